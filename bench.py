@@ -11,11 +11,17 @@ checkpoint, validity bitmap.  With --gpus N (torchrun, one rank per GPU)
 partitions are sharded p -> p % N and the only collective is the final RCCL
 gather of bitmaps + segment summaries to rank 0 (weak scaling).
 
-At N = 1 three more stanzas ride on the same JSON line (configs[2] and [4],
-SURVEY.md §8(d)): `c2` (LZ4 frames, 64 KiB..1 MiB decoded batches, decode +
-CRC + parse), `c5` (skewed 200 B..1 MiB, none/lz4/snappy-java/raw snappy,
-corruptions) and `c6` (C5 plus gzip / zstd), each with its own decode-stage
-roofline and a CPU baseline over the reference's codec libraries.
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure
+needs and no more: generate the C1 job, warm up, time the N steps, write the
+last step's outputs where --dump-outputs asks for them, print the line.
+
+With --full everything else rides on the same JSON line: the segment-index
+rebuild, the C1 CPU baseline, the H2D-inclusive host path and, at N = 1,
+three more stanzas (configs[2] and [4]): `c2` (LZ4 frames,
+64 KiB..1 MiB decoded batches, decode + CRC + parse), `c5` (skewed
+200 B..1 MiB, none/lz4/snappy-java/raw snappy, corruptions) and `c6` (C5
+plus gzip / zstd), each with its own decode-stage roofline and a CPU
+baseline over the reference's codec libraries.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  Only the
 headline's own timed region can cost that line: every stanza, baseline,
@@ -69,6 +75,9 @@ MEMBER_KERNELS = ("k_gzsplan", "k_gzsfind", "k_gzsdecode", "k_gzsresolve", "k_me
 # segment-summary fields that do not depend on where a partition sits in a job
 SUMMARY_JOB_FIELDS = ("n_batches", "terminal_pos", "bytes_consumed", "terminal_errc", "terminal_eof",
                       "has_checkpoint", "first_bad", "ckpt_last_offset", "ckpt_truncate_pos", "n_records")
+# --dump-outputs: rows / bits kept of each output (float64 tables, ~50 MB at the caps)
+DUMP_BATCH_ROWS, DUMP_RECORD_ROWS, DUMP_BITMAP_BITS = 1 << 16, 1 << 18, 1 << 21
+DUMP_SEED = 0xD0
 
 
 def log(*a):
@@ -533,6 +542,62 @@ def job_digest(abi, res) -> str:
     return h.hexdigest()
 
 
+def host_verdicts(abi, out):
+    """A completed job's totals, batch results and validity bitmap on the
+    host (the record index, the bulk of the outputs, stays on the device)."""
+    t = out.totals_host()
+    nb = int(min(t["n_batches"], out.batches.numel() // abi.BATCH_RESULT.itemsize))
+    b = np.frombuffer(out.batches[: nb * abi.BATCH_RESULT.itemsize].cpu().numpy().tobytes(), dtype=abi.BATCH_RESULT)
+    bm = out.bitmap[: (nb + 63) // 64 * 8].cpu().numpy().view(np.uint64)
+    return t, b, bm
+
+
+def _dump_rows(torch, buf, n, dtype, cap, seed):
+    """Up to `cap` rows of a device struct array (all of them, or a seeded
+    ascending sample): (row numbers, rows on the host)."""
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    if n == 0:
+        return idx, np.zeros(0, dtype=dtype)
+    sel = buf[: n * dtype.itemsize].view(n, dtype.itemsize).index_select(0, torch.from_numpy(idx).to(buf.device))
+    return idx, np.frombuffer(sel.cpu().numpy().tobytes(), dtype=dtype)
+
+
+def dump_outputs(dirname, abi, plat, out):
+    """--dump-outputs: what the job's caller receives in `out`, as float64
+    tables (one column per field, in the order named) that two builds can
+    compare file by file:
+      batches.npy   abi.BATCH_COMPARE_FIELDS of the rows in batch_rows.npy
+      records.npy   abi.RECORD_COMPARE_FIELDS of the rows in record_rows.npy
+      summaries.npy abi.SUMMARY_COMPARE_FIELDS, one row per segment
+      totals.npy    n_batches, n_records, decoded_bytes, overflow
+      bitmap.npy    the first validity bits, one float32 each
+    Outputs larger than the DUMP_* caps are sampled (seeded, so the same
+    rows every run).  Every field is an integer below 2^53 here."""
+    os.makedirs(dirname, exist_ok=True)
+    t = out.totals_host()
+    nb = int(min(t["n_batches"], out.batches.numel() // abi.BATCH_RESULT.itemsize))
+    nr = int(min(t["n_records"], out.records.numel() // abi.RECORD_INDEX.itemsize))
+    s = np.frombuffer(out.summaries.cpu().numpy().tobytes(), dtype=abi.SEGMENT_SUMMARY)[: out.n_segments]
+
+    def table(a, fields):
+        return np.stack([a[f].astype(np.float64) for f in fields], axis=1)
+    arrays = {"summaries": table(s, abi.SUMMARY_COMPARE_FIELDS),
+              "totals": np.array([float(t[f]) for f in ("n_batches", "n_records", "decoded_bytes", "overflow")])}
+    for name, buf, n, dtype, cap, fields, seed in (
+            ("batch", out.batches, nb, abi.BATCH_RESULT, DUMP_BATCH_ROWS, abi.BATCH_COMPARE_FIELDS, DUMP_SEED),
+            ("record", out.records, nr, abi.RECORD_INDEX, DUMP_RECORD_ROWS, abi.RECORD_COMPARE_FIELDS, DUMP_SEED + 1)):
+        idx, rows = _dump_rows(plat.torch, buf, n, dtype, cap, seed)
+        arrays[name + "_rows"] = idx.astype(np.float64)
+        arrays[name + ("es" if name == "batch" else "s")] = table(rows, fields)
+    if out.bitmap is not None:
+        bits = min(nb, DUMP_BITMAP_BITS)
+        arrays["bitmap"] = np.unpackbits(out.bitmap[: (bits + 7) // 8].cpu().numpy(),
+                                         bitorder="little")[:bits].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"[dump-outputs] {sum(a.nbytes for a in arrays.values()) >> 20} MiB in {len(arrays)} arrays -> {dirname}")
+
+
 def run_h2d(args, plat, eng, abi, data, seg_bytes, n_parts, flags, ref):
     """H2D-inclusive rate (rpgpu_validate_host): the same C1 partitions,
     host-resident in pinned memory, copied to the device in double-buffered
@@ -646,14 +711,30 @@ def parse_args(argv=None):
                     help="size_bytes per batch (diagnostic; the headline workload is 16 KiB)")
     ap.add_argument("--stats-out", default="",
                     help="write each workload's byte counts (JSON) here, for scripts/parse_traffic.py")
-    ap.add_argument("--workloads", default="c1,h2d,c2,c5,c6",
-                    help="c1 is the headline; h2d (the host path over c1's partitions) and the c2/c5/c6 stanzas run "
-                         "at N = 1 only; a run without c1 is a diagnostic (per-workload profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the segment-index rebuild, the CPU baselines, the H2D host path and the "
+                         "c2/c5/c6 stanzas (each can be switched off by its own option); --check-gather needs it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (batch results, record index, segment "
+                         "summaries, totals, validity bitmap; seeded samples of the large ones) as DIR/<name>.npy")
+    ap.add_argument("--workloads", default=None,
+                    help="default: c1 (the headline), with --full c1,h2d,c2,c5,c6; h2d (the host path over c1's "
+                         "partitions) and the c2/c5/c6 stanzas need --full and run at N = 1 only; a run without c1 is "
+                         "a diagnostic (per-workload profiles)")
     ap.add_argument("--no-h2d", action="store_true", help="skip the H2D-inclusive host-path stanza")
     ap.add_argument("--detail-out", default="",
                     help="write the full stanzas (per-kernel traffic tables, codec splits, descriptions) here; the "
                          "JSON line carries the compact form")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.workloads is None:
+        args.workloads = "c1,h2d,c2,c5,c6" if args.full else "c1"
+    if not args.full and (args.check_gather or set(args.workloads.split(",")) - {"c1", ""}):
+        ap.error("--check-gather and the workloads other than c1 need --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and "c1" not in args.workloads.split(","):
+        ap.error("--dump-outputs writes the headline workload's (c1) outputs")
+    return args
 
 
 def main(argv=None, platform=None):
@@ -815,14 +896,34 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
 
     for _ in range(args.warmup):
         step()
+
+    eng.set_timing(True)
+    if world > 1:
+        dist.barrier()
     plat.sync()
+    t1 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    plat.sync()
+    if world > 1:
+        dist.barrier()
+    t2 = time.perf_counter()
+    eng.set_timing(False)
+    tm = eng.last_timings()
+    elapsed = t2 - t1
+
+    # Everything below is after the headline's timed region and reads the
+    # outputs of its last step.
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     abi, plat, out)
     # correctness of the measured workload (size-independent properties)
-    h = out.to_host()
-    nb = len(h.batches)
-    all_ok = bool(nb == n_batches and (args.no_parse or np.all(h.batches["flags"] & abi.F_PARSE_OK))
-                  and np.all(h.batches["flags"] & abi.F_CRC_OK) and h.totals["overflow"] == 0)
-    bm_ok = bool(np.all(h.bitmap[: nb // 64] == np.uint64(0xFFFFFFFFFFFFFFFF)))
-    n_records = int(h.totals["n_records"])
+    totals, hb, hbm = host_verdicts(abi, out)
+    nb = len(hb)
+    all_ok = bool(nb == n_batches and (args.no_parse or np.all(hb["flags"] & abi.F_PARSE_OK))
+                  and np.all(hb["flags"] & abi.F_CRC_OK) and totals["overflow"] == 0)
+    bm_ok = bool(np.all(hbm[: nb // 64] == np.uint64(0xFFFFFFFFFFFFFFFF)))
+    n_records = int(totals["n_records"])
     gathered = None
     if world > 1:
         # the gathered job picture on rank 0: every partition checkpointed at its end
@@ -843,27 +944,13 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
         if rank == 0:
             gathered = dict(gathered or {}, bytes_per_step=int(sum(max(sz) * world for sz in sizes)),
                             backend=args.dist_backend)
-    payload_bytes = int(np.sum(h.batches["size_bytes"].astype(np.int64) - abi.HEADER_SIZE))
-    seg_total = int(np.sum(h.batches["size_bytes"].astype(np.int64)))
-    del h
+    payload_bytes = int(np.sum(hb["size_bytes"].astype(np.int64) - abi.HEADER_SIZE))
+    seg_total = int(np.sum(hb["size_bytes"].astype(np.int64)))
+    del hb, hbm
     if rank == 0:
         write_stats(args, "c1", {"stored": seg_total, "stored_payload": payload_bytes, "compressed_in": 0, "decoded": 0,
                                  "batches": n_batches, "compressed_batches": 0, "records": n_records})
 
-    eng.set_timing(True)
-    if world > 1:
-        dist.barrier()
-    plat.sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    plat.sync()
-    if world > 1:
-        dist.barrier()
-    t2 = time.perf_counter()
-    eng.set_timing(False)
-    tm = eng.last_timings()
-    elapsed = t2 - t1
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=comm)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -876,8 +963,8 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
     ms_per_step = elapsed / args.steps * 1e3
     value = job_bytes * args.steps / elapsed / 1e9
 
-    # Everything below is after the headline's timed region: each leg
-    # reports a failure in its own field instead of costing the line.
+    # Each leg below reports a failure in its own field instead of costing
+    # the line; the legs that take runs of their own need --full.
 
     # roofline of the dominant kernel (k_validate: CRC32C of every stored
     # payload): algorithmic bytes per launch = payload read once + 128 B per
@@ -899,7 +986,7 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
     # recovered batches, §8(f) row 2): timed separately on its own stream,
     # after the headline region; not part of `value`
     index, index_res = None, None
-    if not args.no_index:
+    if args.full and not args.no_index:
         try:
             bases = [0] * len(parts)
             ms, index_res = plat.time_on_side_stream(
@@ -931,13 +1018,14 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
                               seg_bytes)
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and host_first is not None:
+    if rank == 0 and args.full and not args.no_cpu_baseline and host_first is not None:
         try:
             cpu = cpu_baseline_c1(host_first)
         except Exception as e:
             cpu = failure("c1 cpu baseline", e)
+    run_host_path = args.full and world == 1 and not args.no_h2d and "h2d" in args.workloads.split(",")
     dev_digest = None
-    if world == 1 and not args.no_h2d and "h2d" in args.workloads.split(","):
+    if run_host_path:
         try:
             dev_digest = job_digest(abi, out.to_host())
         except Exception:
@@ -946,7 +1034,7 @@ def run_c1(args, plat, dist, eng, abi, world, rank):
     del out, d_offs, payload, index_res
     plat.empty_cache()
     h2d = None
-    if world == 1 and not args.no_h2d and "h2d" in args.workloads.split(","):
+    if run_host_path:
         try:
             h2d = run_h2d(args, plat, eng, abi, data, seg_bytes, len(parts), flags, (n_batches, n_records, dev_digest))
         except Exception as e:

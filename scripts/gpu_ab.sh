@@ -6,6 +6,8 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=$1
 shift
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 for i in 1 2; do
 for spec in "$@"; do
 name=${spec%%=*}
@@ -17,9 +19,9 @@ envs=""
 unset RPGPU_VARIANT
 [ "$var" != cur ] && export RPGPU_VARIANT=$var
 for kv in ${envs//,/ }; do export "$kv"; done
-timeout -k 10 300 python -u bench.py --workloads ${W:-c2,c5} --no-cpu-baseline --no-index --steps 10 --warmup 2 > gpurun_out/ab_${TAG}_${name}_$i.json 2> gpurun_out/ab_${TAG}_${name}_$i.err
-) || { tail -30 gpurun_out/ab_${TAG}_${name}_$i.err; exit 1; }
-python - gpurun_out/ab_${TAG}_${name}_$i.json $name <<'PY'
+timeout -k 10 300 python -u bench.py --full --workloads ${W:-c2,c5} --no-cpu-baseline --no-index --steps 10 --warmup 2 > $OUT/ab_${TAG}_${name}_$i.json 2> $OUT/ab_${TAG}_${name}_$i.err
+) || { tail -30 $OUT/ab_${TAG}_${name}_$i.err; exit 1; }
+python - $OUT/ab_${TAG}_${name}_$i.json $name <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 c = j["config"]

@@ -6,12 +6,14 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-r04}
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 for G in records index bitmap; do
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
   --master-port 29531 bench.py --gpus 2 --steps 5 --warmup 2 --seg-gib 0.25 --dist-backend gloo \
-  --gather $G --check-gather --no-cpu-baseline > gpurun_out/bench_n2_${G}_$TAG.json 2> gpurun_out/bench_n2_${G}_$TAG.err \
-  || { tail -40 gpurun_out/bench_n2_${G}_$TAG.err; exit 1; }
-python - gpurun_out/bench_n2_${G}_$TAG.json <<'PY'
+  --full --gather $G --check-gather --no-cpu-baseline > $OUT/bench_n2_${G}_$TAG.json 2> $OUT/bench_n2_${G}_$TAG.err \
+  || { tail -40 $OUT/bench_n2_${G}_$TAG.err; exit 1; }
+python - $OUT/bench_n2_${G}_$TAG.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 c = j["config"]
@@ -19,6 +21,6 @@ print(sys.argv[1], "value", j["value"], "gather_check", c["gather_check"], "gath
 PY
 done
 if [ "${2:-}" = "n1" ]; then
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -30 gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
+cat $OUT/bench_$TAG.json
 fi

@@ -1,11 +1,13 @@
-# The default bench's stanzas (c1,h2d,c2,c5,c6) under two side-stream
+# The full bench's stanzas (c1,h2d,c2,c5,c6) under two side-stream
 # setups (diagnostics): the product, and the diagnostic build with the side
 # stream at default priority (RPGPU_SIDE_PRIO=0)
 set -e
 cd "$GRAFT_REPO_ROOT"
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 run() {
-timeout -k 10 600 env $3 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/ord_$2.json 2> gpurun_out/ord_$2.err || { tail -5 gpurun_out/ord_$2.err; exit 1; }
-python3 - gpurun_out/ord_$2.json $2 <<'PY'
+timeout -k 10 600 env $3 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/ord_$2.json 2> $OUT/ord_$2.err || { tail -5 $OUT/ord_$2.err; exit 1; }
+python3 - $OUT/ord_$2.json $2 <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=j['config']
 print(sys.argv[2], 'c1', j['ms_per_step'])

@@ -4,7 +4,7 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-sql}
-J="python3 bench.py --workloads c2 --steps 1 --warmup 0 --no-cpu-baseline --no-index"
+J="python3 bench.py --full --workloads c2 --steps 1 --warmup 0 --no-cpu-baseline --no-index"
 timeout -s KILL 180 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_k -o k --output-format csv -- $J > gpurun_out/${TAG}_k.log 2>&1
 echo "pass k ok"
 timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU -d gpurun_out/${TAG}_a -o a --output-format csv -- $J > gpurun_out/${TAG}_a.log 2>&1

@@ -7,13 +7,15 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-r03}
+export OUT=${OUT:-bench_out}  # scripts/parse_traffic.py reads the same folder
+mkdir -p "$OUT"
 if [ -z "${NO_TRACE:-}" ]; then
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o $TAG --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-index > gpurun_out/prof_$TAG.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o $TAG --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-index > $OUT/prof_$TAG.log 2>&1
 echo "trace ok"
 fi
 for W in ${WORKLOADS:-c1 c2 c5 c6}; do
-timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_${TAG}_$W -o f --output-format csv -- python3 bench.py --workloads $W --steps 2 --warmup 1 --no-cpu-baseline --no-index --stats-out gpurun_out/stats_${TAG}_$W.json > gpurun_out/pmc_fetch_${TAG}_$W.log 2>&1
+timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch_${TAG}_$W -o f --output-format csv -- python3 bench.py --full --workloads $W --steps 2 --warmup 1 --no-cpu-baseline --no-index --stats-out $OUT/stats_${TAG}_$W.json > $OUT/pmc_fetch_${TAG}_$W.log 2>&1
 echo "fetch $W ok"
-timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_${TAG}_$W -o w --output-format csv -- python3 bench.py --workloads $W --steps 2 --warmup 1 --no-cpu-baseline --no-index > gpurun_out/pmc_write_${TAG}_$W.log 2>&1
+timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write_${TAG}_$W -o w --output-format csv -- python3 bench.py --full --workloads $W --steps 2 --warmup 1 --no-cpu-baseline --no-index > $OUT/pmc_write_${TAG}_$W.log 2>&1
 echo "write $W ok"
 done

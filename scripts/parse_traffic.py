@@ -22,7 +22,7 @@ import sys
 from collections import defaultdict
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = os.path.join(root, "gpurun_out")
+out = os.path.join(root, os.environ.get("OUT", "bench_out"))  # where scripts/gpu_traffic.sh wrote
 prof = os.path.join(root, "profiles")
 
 

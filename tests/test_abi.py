@@ -24,7 +24,7 @@ def test_every_declared_symbol_is_exported(rplib):
         assert f" T {n}\n" in out or f" W {n}\n" in out, n
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     src = r'''
 #include "rpgpu.h"
 #include <stddef.h>
@@ -35,7 +35,7 @@ int main(void) {
          offsetof(rpgpu_record_index, end_pos), offsetof(rpgpu_job, d_valid_bitmap));
   return 0;
 }'''
-    exe = "/tmp/rpgpu_layout_check"
+    exe = str(tmp_path / "rpgpu_layout_check")
     r = subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src,
                        text=True, capture_output=True)
     assert r.returncode == 0, r.stderr

@@ -247,7 +247,7 @@ def env1(monkeypatch):
 
 
 def test_bench_single_rank_all_stanzas(env1, rplib, tmp_path):
-    lines = _run_bench(["--steps", "1", "--warmup", "1", "--seg-gib", str(2 / 1024), "--partitions", "2",
+    lines = _run_bench(["--full", "--steps", "1", "--warmup", "1", "--seg-gib", str(2 / 1024), "--partitions", "2",
                         "--detail-out", str(tmp_path / "detail.json")])
     assert len(lines) == 1
     # the driver keeps the last 8 KB of stdout: the whole line must fit well inside
@@ -282,10 +282,92 @@ def test_bench_stanza_failure_keeps_headline(env1, rplib, monkeypatch):
     def boom(*a, **k):
         raise RuntimeError("stanza exploded")
     monkeypatch.setattr(bench, "run_compressed", boom)
-    lines = _run_bench(["--steps", "1", "--warmup", "0", "--seg-gib", str(1 / 1024), "--partitions", "1",
+    lines = _run_bench(["--full", "--steps", "1", "--warmup", "0", "--seg-gib", str(1 / 1024), "--partitions", "1",
                         "--no-cpu-baseline", "--workloads", "c1,c2"])
     j = json.loads(lines[0])
     assert j["value"] is not None and j["ms_per_step"] > 0 and "stanza exploded" in j["config"]["c2"]["error"]
+
+
+PLAIN = ["--gpus", "1", "--steps", "2", "--warmup", "0", "--seg-gib", str(2 / 1024), "--partitions", "2"]
+
+
+def test_bench_plain_run_is_lean(env1, rplib, monkeypatch):
+    """Without --full only the headline runs: no stanza, host path, segment
+    index or CPU baseline (each would raise here), and the line still carries
+    the headline's fields -- also with no warm-up step."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def boom(*a, **k):
+        raise AssertionError("a plain run left the headline's path")
+    for leg in ("run_compressed", "run_h2d", "cpu_baseline_c1", "cpu_baseline_decode", "check_gather"):
+        monkeypatch.setattr(bench, leg, boom)
+    monkeypatch.setattr(CpuPlatform, "time_on_side_stream", boom)
+    lines = _run_bench(PLAIN)
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["unit"] == "GB/s" and j["higher_is_better"] is True and j["dtype"] == "u8" and j["steps"] == 2
+    assert j["value"] > 0 and j["ms_per_step"] > 0
+    # value = job bytes per step / time per step (the line rounds it to 0.01)
+    assert j["value"] == pytest.approx(2 * (2 << 20) / (j["ms_per_step"] * 1e-3) / 1e9, rel=1e-3, abs=0.006)
+    c = j["config"]
+    assert c["parity"] == {"all_batches_valid": True, "bitmap_all_ones": True}
+    assert not j["cpu_baseline"] and c["segment_index"] is None
+    assert not {"h2d", "c2", "c5", "c6"} & set(c)
+    assert j["roofline"]["kernel_ms"] > 0
+
+
+@pytest.mark.parametrize("argv", [["--workloads", "c1,c2"], ["--check-gather"], ["--steps", "0"],
+                                  ["--full", "--workloads", "c2", "--dump-outputs", "x"]])
+def test_bench_rejects_options_that_need_more(argv):
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(argv)
+
+
+def test_bench_dump_outputs(env1, rplib, tmp_path, monkeypatch):
+    """--dump-outputs: the last step's outputs as float32 / float64 .npy
+    files that equal the oracle's job over the same seeded input, identical
+    from run to run, sampled (same rows every run) above the caps."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import synth
+    from redpanda_amd import abi
+    monkeypatch.setattr(bench, "DUMP_RECORD_ROWS", 100)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert len(_run_bench(PLAIN + ["--dump-outputs", str(a)])) == 1
+    assert len(_run_bench(PLAIN + ["--dump-outputs", str(b)])) == 1
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["batch_rows.npy", "batches.npy", "bitmap.npy", "record_rows.npy", "records.npy",
+                     "summaries.npy", "totals.npy"]
+    got = {n[:-4]: np.load(a / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[n[:-4]], np.load(b / n)), n
+    assert sum(x.nbytes for x in got.values()) < 64e6
+    # the same job through the oracle
+    segs = []
+    for p in range(2):
+        s = np.zeros(2 << 20, dtype=np.uint8)
+        synth.gen_segment(s, p, **synth.C1)
+        segs.append(s)
+    offs = np.arange(3, dtype=np.uint64) * np.uint64(2 << 20)
+    from oracle import oracle as O
+    ref = O.run_job(np.concatenate(segs), offs, abi.JOB_CRC | abi.JOB_PARSE)
+    nb, nr = len(ref.batches), len(ref.records)
+    assert nb > 0 and nr > 100
+    assert list(got["totals"][:2]) == [nb, nr]
+    assert np.array_equal(got["batch_rows"], np.arange(nb))
+    for k, f in enumerate(abi.BATCH_COMPARE_FIELDS):
+        assert np.array_equal(got["batches"][:, k], ref.batches[f].astype(np.float64)), f
+    rows = got["record_rows"].astype(np.int64)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and rows[-1] < nr
+    for k, f in enumerate(abi.RECORD_COMPARE_FIELDS):
+        assert np.array_equal(got["records"][:, k], ref.records[f][rows].astype(np.float64)), f
+    for k, f in enumerate(abi.SUMMARY_COMPARE_FIELDS):
+        assert np.array_equal(got["summaries"][:, k], ref.summaries[f].astype(np.float64)), f
+    assert got["bitmap"].shape == (nb,) and np.all(got["bitmap"] == 1)
 
 
 def _free_port():
@@ -297,7 +379,7 @@ def _free_port():
 def _rank_worker(rank, world, port, gather, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank),
                       LOCAL_RANK=str(rank), OMP_NUM_THREADS="1")
-    lines = _run_bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--seg-gib", str(1 / 1024),
+    lines = _run_bench(["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--seg-gib", str(1 / 1024),
                         "--partitions", "2", "--dist-backend", "gloo", "--gather", gather, "--check-gather",
                         "--no-cpu-baseline"])
     with open(os.path.join(out_dir, f"rank{rank}.json"), "w") as f:

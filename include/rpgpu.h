@@ -502,6 +502,143 @@ uint64_t rpgpu_uncompress_bound(int codec, const void* in, size_t n);
 int rpgpu_stamp_host(rpgpu_ctx* ctx, uint8_t* buf, size_t len, const uint64_t* pos, const uint32_t* payload_len,
                      uint32_t n, int64_t next_offset, uint32_t flags);
 
+/* ------------------------------------------------------------------------ */
+/* Key compaction of segments (storage::internal::self_compact_segment's     */
+/* three reducers: compaction_key_reducer, compacted_offset_list_reducer and */
+/* copy_data_segment_reducer, storage/compaction_reducers.cc:34-222,         */
+/* storage/segment_utils.cc:197-201, :306-365).                              */
+/* ------------------------------------------------------------------------ */
+/* rpgpu_compact_segment.status */
+enum rpgpu_compact_status {
+    RPGPU_COMPACT_OK = 0,
+    /* summary.first_bad != n_batches, or a batch lacks one of HEADER_OK,
+     * COMPLETE, CRC_OK, PARSED, PARSE_OK, INDEX_WRITTEN (CODEC_OK when
+     * compressed) or has DECODE_OVERFLOW, or the source job overflowed: the
+     * reference throws or asserts on such a batch */
+    RPGPU_COMPACT_NOT_CLEAN = 1,
+    /* record offsets base_offset + offset_delta are not strictly increasing in
+     * natural order (batch chain order, then record order), or one of them
+     * does not fit [0, 2^32) relative to the first batch's base_offset: the
+     * reference's result then depends on how compacted_offset_list aliases
+     * offsets, which real segments never show */
+    RPGPU_COMPACT_OFFSETS = 2,
+};
+/* spill_key_index::max_key_size (storage/spill_key_index.h:36): keys are
+ * compared by their first 65515 bytes */
+#define RPGPU_COMPACT_MAX_KEY 65515u
+
+#define RPGPU_COMPACT_F_REWRITTEN (1u << 0) /* some records dropped: payload re-encoded, header rebuilt */
+
+/* One entry per batch of the compacted output, in output order.  32 bytes. */
+typedef struct rpgpu_compact_batch {
+    uint64_t out_pos;      /* header position in d_out */
+    uint32_t src_batch;    /* job-wide ordinal of the source batch */
+    uint32_t payload_len;  /* bytes after the 61-byte header */
+    uint32_t codec;        /* the source batch's codec (rpgpu_codec); the output is never compressed */
+    uint32_t kept;         /* records in the output batch */
+    uint32_t flags;        /* RPGPU_COMPACT_F_* */
+    uint32_t reserved;
+} rpgpu_compact_batch;
+
+/* Per segment.  56 bytes. */
+typedef struct rpgpu_compact_segment {
+    uint32_t status;       /* rpgpu_compact_status; not OK: empty output, no keep bits */
+    uint32_t reserved;
+    uint64_t records_in;   /* records of the segment (0 unless OK) */
+    uint64_t records_kept;
+    uint64_t batches_in;
+    uint64_t batches_out;
+    uint64_t batches_rewritten;
+    uint64_t bytes_out;
+} rpgpu_compact_segment;
+
+/* Whole call.  88 bytes. */
+typedef struct rpgpu_compact_totals {
+    uint64_t records_in, records_kept, batches_in, batches_out, batches_rewritten, bytes_out;
+    uint64_t out_capacity_needed;        /* bytes_out + 16 */
+    uint64_t out_batch_capacity_needed;  /* batches_out */
+    uint32_t overflow;                   /* bit 0: out_capacity, bit 1: out_batch_capacity too small; nothing
+                                            is then written to d_out / d_out_batches */
+    uint32_t key_compare_mismatches;     /* key table slots whose tag matched a record of another key
+                                            (resolved by comparing the key bytes; a count of work, not an
+                                            error, and not reproducible from run to run) */
+    uint64_t reserved[2];
+} rpgpu_compact_totals;
+
+/* All pointers are DEVICE pointers, caller-owned.  The first block is the
+ * input and the outputs of a completed disk-layout rpgpu_submit with
+ * RPGPU_JOB_CRC | RPGPU_JOB_PARSE | RPGPU_JOB_DECODE (same stream, or
+ * synchronised). */
+typedef struct rpgpu_compact_job {
+    const uint8_t* d_data;
+    const uint64_t* d_seg_offsets;       /* n_segments + 1 */
+    uint32_t n_segments;
+    uint32_t reserved;
+    const rpgpu_batch_result* d_batches;
+    uint64_t batch_capacity;             /* a bound of the source job's totals.n_batches (its batch_capacity, or
+                                            the total itself): sizes grids and scratch */
+    const rpgpu_record_index* d_records;
+    uint64_t record_capacity;            /* likewise for totals.n_records; below 2^32 - 1 */
+    const uint8_t* d_decoded;            /* may be NULL when no batch is compressed */
+    const rpgpu_segment_summary* d_summaries;
+    const rpgpu_job_totals* d_totals;
+    /* outputs */
+    uint64_t* d_keep;                    /* (record_capacity + 63) / 64 words: bit i = record-index slot i survives;
+                                            zeroed by the call */
+    uint8_t* d_out;                      /* the compacted segments back to back; 16-byte aligned */
+    uint64_t out_capacity;               /* bytes, including 16 spare bytes past the last batch.  The sum of
+                                            (61 + decoded_len) over the job's batches, plus 16, is always enough,
+                                            except for a record whose header count runs past the end of its
+                                            payload: the reference materialises that many empty headers and
+                                            append_record_to_buffer writes two bytes for each */
+    uint64_t* d_out_seg_offsets;         /* n_segments + 1: segment s's output is [s, s + 1) */
+    rpgpu_compact_batch* d_out_batches;
+    uint64_t out_batch_capacity;
+    rpgpu_compact_segment* d_seg;        /* n_segments */
+    rpgpu_compact_totals* d_ctotals;     /* one */
+} rpgpu_compact_job;
+
+/* For every segment of the job: which records survive key compaction, and
+ * the compacted segment, i.e. the batches copy_data_segment_reducer::filter
+ * returns, in order, back to back, headers stamped
+ * (reset_size_checksum_metadata + header_crc).
+ *   keep set   compaction_key_reducer with unbounded memory (its eviction
+ *              under _max_mem only ever keeps more and follows absl's
+ *              iteration order: not reproduced), then compacted_offset_list:
+ *              per segment, of the records sharing a key (the first
+ *              min(key_len, 65515) key bytes; null and empty are one key) the
+ *              last in natural order survives.  Keys never match across
+ *              segments; the batch type plays no part.
+ *   filter     no record kept: the batch is dropped.  All kept: the batch
+ *              passes with its (decoded) payload verbatim, a compressed one in
+ *              its decompress_batch form (compression bits cleared, size / crc
+ *              / header_crc reset = decoded_crc / decoded_header_crc).
+ *              Otherwise the payload is append_record_to_buffer over the kept
+ *              records (varints re-encoded canonically, the length field kept
+ *              as parsed) and the header gets first_timestamp += ts_delta of
+ *              the first kept record, max_timestamp = new first_timestamp +
+ *              ts_delta of the last kept one unless attrs bit 3 (log append
+ *              time) is set, record_count, compression bits cleared.
+ * Recompression (do_compaction's compress_batch) is left to the caller:
+ * every output batch reports its source codec for rpgpu_compress_batch.
+ * A segment that is not eligible (rpgpu_compact_status) gets an empty output
+ * and no keep bits; a segment without batches is OK and empty.
+ * Asynchronous on `stream`; never writes out of bounds: a capacity that is
+ * too small sets d_ctotals->overflow and reports the sizes needed.  NULL or
+ * inconsistent arguments return RPGPU_E_INVALID without touching a device. */
+int rpgpu_compact(rpgpu_ctx* ctx, const rpgpu_compact_job* job, void* stream);
+
+/* sizeof of the compaction structs as compiled into the library: 0 =
+ * rpgpu_compact_batch, 1 = rpgpu_compact_segment, 2 = rpgpu_compact_totals,
+ * 3 = rpgpu_compact_job (0 for any other value). */
+size_t rpgpu_compact_sizeof(int which);
+
+/* Device time of the last timed rpgpu_compact (rpgpu_set_timing), in
+ * milliseconds: 0 = whole call, 1 = eligibility + key insert, 2 = keep pass,
+ * 3 = size pass + scans, 4 = write pass, 5 = stamp.  Synchronises on the
+ * call's last event. */
+int rpgpu_compact_timings(rpgpu_ctx* ctx, float* ms, int n);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -929,6 +929,130 @@ public:
     }
 };
 
+namespace internal {
+
+// What self_compact_segment's reducers leave of one segment
+// (storage/segment_utils.cc:306-365, storage/compaction_reducers.cc).
+struct compacted_segment {
+    std::vector<uint8_t> bytes;              // copy_data_segment_reducer::filter's batches, back to back, stamped
+    std::vector<int64_t> kept_offsets;       // compacted_offset_list: the surviving record offsets, ascending
+    std::vector<model::compression> codecs;  // per output batch: its codec before compaction (the batches are
+                                             // written uncompressed; do_compaction's compress_batch is the
+                                             // caller's, e.g. compression::compressor::compress)
+    rpgpu_compact_segment stats{};
+};
+
+// Key compaction of one disk-layout segment on the device: rpgpu_submit
+// (CRC | PARSE | DECODE) then rpgpu_compact over its outputs.  Throws
+// std::runtime_error where the segment is not eligible (a batch fails crc,
+// decode or parse, or record offsets do not increase): the reference's path
+// throws or asserts there.
+inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::engine& e = rpgpu::engine::local()) {
+    rpgpu_ctx* c = e.ctx();
+    rpgpu::dev_buffer d_data(e, len + 16), d_offs(e, 16);
+    const uint64_t offs[2] = {0, (uint64_t)len};
+    e.check(rpgpu_memset(c, (uint8_t*)d_data.get() + len, 0, 16, nullptr), "rpgpu_memset");
+    if (len) e.check(rpgpu_memcpy_h2d(c, d_data.get(), seg, len, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_offs.get(), offs, sizeof offs, nullptr), "rpgpu_memcpy_h2d");
+    rpgpu_job j{};
+    j.d_data = (const uint8_t*)d_data.get();
+    j.d_seg_offsets = (const uint64_t*)d_offs.get();
+    j.h_seg_offsets = offs;
+    j.n_segments = 1;
+    j.layout = RPGPU_LAYOUT_DISK;
+    j.flags = RPGPU_JOB_CRC | RPGPU_JOB_PARSE | RPGPU_JOB_DECODE;
+    rpgpu_capacity cap{};
+    e.check(rpgpu_query_capacity(c, &j, nullptr, &cap), "rpgpu_query_capacity");
+    const uint64_t nb = cap.n_batches + 1, nr = cap.record_capacity + 1, nd = cap.decoded_capacity + 16;
+    rpgpu::dev_buffer d_b(e, nb * sizeof(rpgpu_batch_result)), d_r(e, nr * sizeof(rpgpu_record_index)), d_dec(e, nd),
+        d_sum(e, sizeof(rpgpu_segment_summary)), d_tot(e, sizeof(rpgpu_job_totals));
+    j.d_batches = (rpgpu_batch_result*)d_b.get();
+    j.batch_capacity = nb;
+    j.d_records = (rpgpu_record_index*)d_r.get();
+    j.record_capacity = nr;
+    j.d_decoded = (uint8_t*)d_dec.get();
+    j.decoded_capacity = nd;
+    j.d_summaries = (rpgpu_segment_summary*)d_sum.get();
+    j.d_totals = (rpgpu_job_totals*)d_tot.get();
+    e.check(rpgpu_submit(c, &j, nullptr), "rpgpu_submit");
+    rpgpu_job_totals t{};
+    e.check(rpgpu_memcpy_d2h(c, &t, d_tot.get(), sizeof t, nullptr), "rpgpu_memcpy_d2h");
+    e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+    if (t.overflow) throw std::runtime_error("compact_segment: the validation job overflowed its outputs");
+    std::vector<rpgpu_batch_result> batches((size_t)t.n_batches);
+    std::vector<rpgpu_record_index> records((size_t)t.n_records);
+    if (!batches.empty())
+        e.check(rpgpu_memcpy_d2h(c, batches.data(), d_b.get(), batches.size() * sizeof(rpgpu_batch_result), nullptr),
+                "rpgpu_memcpy_d2h");
+    if (!records.empty())
+        e.check(rpgpu_memcpy_d2h(c, records.data(), d_r.get(), records.size() * sizeof(rpgpu_record_index), nullptr),
+                "rpgpu_memcpy_d2h");
+    e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+    // always enough: every batch at its decoded size, plus the spare bytes
+    uint64_t out_cap = 16;
+    for (const auto& b : batches) out_cap += RPGPU_HEADER_SIZE + (uint64_t)b.decoded_len;
+    const uint64_t words = (t.n_records + 63) / 64;
+    compacted_segment res;
+    rpgpu_compact_totals ct{};
+    std::vector<uint64_t> keep((size_t)words);
+    std::vector<rpgpu_compact_batch> ob;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        rpgpu::dev_buffer d_keep(e, words * 8 + 8), d_out(e, out_cap), d_oso(e, 16),
+            d_ob(e, (batches.size() + 1) * sizeof(rpgpu_compact_batch)), d_seg(e, sizeof(rpgpu_compact_segment)),
+            d_ct(e, sizeof(rpgpu_compact_totals));
+        rpgpu_compact_job k{};
+        k.d_data = j.d_data;
+        k.d_seg_offsets = j.d_seg_offsets;
+        k.n_segments = 1;
+        k.d_batches = j.d_batches;
+        k.batch_capacity = t.n_batches;
+        k.d_records = j.d_records;
+        k.record_capacity = t.n_records;
+        k.d_decoded = j.d_decoded;
+        k.d_summaries = j.d_summaries;
+        k.d_totals = j.d_totals;
+        k.d_keep = (uint64_t*)d_keep.get();
+        k.d_out = (uint8_t*)d_out.get();
+        k.out_capacity = out_cap;
+        k.d_out_seg_offsets = (uint64_t*)d_oso.get();
+        k.d_out_batches = (rpgpu_compact_batch*)d_ob.get();
+        k.out_batch_capacity = batches.size();
+        k.d_seg = (rpgpu_compact_segment*)d_seg.get();
+        k.d_ctotals = (rpgpu_compact_totals*)d_ct.get();
+        e.check(rpgpu_compact(c, &k, nullptr), "rpgpu_compact");
+        e.check(rpgpu_memcpy_d2h(c, &ct, d_ct.get(), sizeof ct, nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_memcpy_d2h(c, &res.stats, d_seg.get(), sizeof res.stats, nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        if (ct.overflow) {  // only a record announcing headers past its payload's end outgrows the bound
+            if (attempt) throw std::runtime_error("compact_segment: output capacity");
+            out_cap = ct.out_capacity_needed;
+            continue;
+        }
+        res.bytes.resize((size_t)ct.bytes_out);
+        ob.resize((size_t)ct.batches_out);
+        if (!res.bytes.empty())
+            e.check(rpgpu_memcpy_d2h(c, res.bytes.data(), d_out.get(), res.bytes.size(), nullptr), "rpgpu_memcpy_d2h");
+        if (!ob.empty())
+            e.check(rpgpu_memcpy_d2h(c, ob.data(), d_ob.get(), ob.size() * sizeof(rpgpu_compact_batch), nullptr),
+                    "rpgpu_memcpy_d2h");
+        if (words) e.check(rpgpu_memcpy_d2h(c, keep.data(), d_keep.get(), (size_t)words * 8, nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        break;
+    }
+    if (res.stats.status == RPGPU_COMPACT_NOT_CLEAN)
+        throw std::runtime_error("compact_segment: a batch of the segment fails crc, decode or parse");
+    if (res.stats.status != RPGPU_COMPACT_OK)
+        throw std::runtime_error("compact_segment: record offsets are not strictly increasing");
+    for (size_t i = 0; i < records.size(); i++)
+        if ((keep[i >> 6] >> (i & 63)) & 1)
+            res.kept_offsets.push_back(
+              (int64_t)((uint64_t)batches[records[i].batch].base_offset + (uint64_t)(int64_t)records[i].offset_delta));
+    for (const auto& b : ob) res.codecs.push_back(static_cast<model::compression>(b.codec));
+    return res;
+}
+
+}  // namespace internal
+
 }  // namespace storage
 
 // ---------------------------------------------------------------------------

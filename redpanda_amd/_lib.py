@@ -41,6 +41,19 @@ class CapacityC(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class CompactJobC(C.Structure):
+    """rpgpu_compact_job (include/rpgpu.h)."""
+    _fields_ = [
+        ("d_data", C.c_void_p), ("d_seg_offsets", C.c_void_p), ("n_segments", C.c_uint32), ("reserved", C.c_uint32),
+        ("d_batches", C.c_void_p), ("batch_capacity", C.c_uint64),
+        ("d_records", C.c_void_p), ("record_capacity", C.c_uint64),
+        ("d_decoded", C.c_void_p), ("d_summaries", C.c_void_p), ("d_totals", C.c_void_p),
+        ("d_keep", C.c_void_p), ("d_out", C.c_void_p), ("out_capacity", C.c_uint64),
+        ("d_out_seg_offsets", C.c_void_p), ("d_out_batches", C.c_void_p), ("out_batch_capacity", C.c_uint64),
+        ("d_seg", C.c_void_p), ("d_ctotals", C.c_void_p),
+    ]
+
+
 def exported_symbols_from_header(path: str = HEADER):
     """Function names declared in include/rpgpu.h."""
     src = open(path).read()
@@ -104,6 +117,9 @@ def load():
         "rpgpu_segment_index": (i32, [vp, vp, u64, vp, u32, u64, vp, vp, vp, vp, vp]),
         "rpgpu_uncompress_bound": (u64, [i32, vp, sz]),
         "rpgpu_stamp_host": (i32, [vp, vp, sz, vp, vp, u32, C.c_int64, u32]),
+        "rpgpu_compact": (i32, [vp, C.POINTER(CompactJobC), vp]),
+        "rpgpu_compact_sizeof": (sz, [i32]),
+        "rpgpu_compact_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -132,5 +148,5 @@ def crc32c(data, crc: int = 0) -> int:
     return load().rpgpu_crc32c_extend(crc, a.ctypes.data_as(C.c_void_p), a.nbytes)
 
 
-__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "RpgpuError", "abi",
+__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "RpgpuError", "abi",
            "exported_symbols_from_header"]

@@ -97,6 +97,33 @@ JOB_TOTALS = np.dtype([
 ])
 assert JOB_TOTALS.itemsize == 72
 
+# rpgpu_compact (include/rpgpu.h): key compaction of segments
+COMPACT_OK, COMPACT_NOT_CLEAN, COMPACT_OFFSETS = 0, 1, 2
+COMPACT_MAX_KEY = 65515  # spill_key_index::max_key_size (storage/spill_key_index.h:36)
+COMPACT_F_REWRITTEN = 1 << 0
+
+COMPACT_BATCH = np.dtype([
+    ("out_pos", "<u8"), ("src_batch", "<u4"), ("payload_len", "<u4"), ("codec", "<u4"), ("kept", "<u4"),
+    ("flags", "<u4"), ("reserved", "<u4"),
+])
+assert COMPACT_BATCH.itemsize == 32
+COMPACT_SEGMENT = np.dtype([
+    ("status", "<u4"), ("reserved", "<u4"), ("records_in", "<u8"), ("records_kept", "<u8"), ("batches_in", "<u8"),
+    ("batches_out", "<u8"), ("batches_rewritten", "<u8"), ("bytes_out", "<u8"),
+])
+assert COMPACT_SEGMENT.itemsize == 56
+COMPACT_TOTALS = np.dtype([
+    ("records_in", "<u8"), ("records_kept", "<u8"), ("batches_in", "<u8"), ("batches_out", "<u8"),
+    ("batches_rewritten", "<u8"), ("bytes_out", "<u8"), ("out_capacity_needed", "<u8"),
+    ("out_batch_capacity_needed", "<u8"), ("overflow", "<u4"), ("key_compare_mismatches", "<u4"),
+    ("reserved", "<u8", (2,)),
+])
+assert COMPACT_TOTALS.itemsize == 88
+COMPACT_BATCH_COMPARE_FIELDS = [n for n in COMPACT_BATCH.names if n != "reserved"]
+COMPACT_SEGMENT_COMPARE_FIELDS = [n for n in COMPACT_SEGMENT.names if n != "reserved"]
+# key_compare_mismatches counts work (it depends on the insertion order), not a result
+COMPACT_TOTALS_COMPARE_FIELDS = [n for n in COMPACT_TOTALS.names if n not in ("reserved", "key_compare_mismatches")]
+
 # fields of rpgpu_batch_result that are outputs of the engine and compared
 # bit-exactly against the oracle (reserved fields excluded)
 BATCH_COMPARE_FIELDS = [n for n in BATCH_RESULT.names if not n.startswith("reserved")]

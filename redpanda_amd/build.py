@@ -20,7 +20,8 @@ OUT = os.path.join(HERE, "librpgpu.so")
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("RPGPU_ARCH", "gfx950")
 
-HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_runtime.hip"]
+HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip",
+               "rp_runtime.hip"]
 CXX_SOURCES = ["rp_hostcodec.cpp"]
 
 
@@ -113,7 +114,23 @@ def build_surfaces_test(force: bool = False) -> str:
     return SURFACES_BIN
 
 
-ZSHOST_SRC = os.path.join(ROOT, "tests", "cpp", "zstd_core_host.cpp")
+COMPACT_SRC = os.path.join(ROOT, "tests", "cpp", "compact_main.cpp")
+COMPACT_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "compact_test")
+
+
+def build_compact_test(force: bool = False) -> str:
+    """Host driver of storage::internal::compact_segment
+    (include/rpgpu_redpanda.h), linked like the surfaces driver."""
+    lib = build()
+    hdrs = [os.path.join(INC, "rpgpu.h"), os.path.join(INC, "rpgpu_redpanda.h")]
+    if force or _stale(COMPACT_BIN, [COMPACT_SRC, lib] + hdrs):
+        os.makedirs(os.path.dirname(COMPACT_BIN), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, COMPACT_SRC, "-o", COMPACT_BIN, "-L", HERE, "-l:librpgpu.so",
+              "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
+    return COMPACT_BIN
+
+
+ZSHOST_SRC =os.path.join(ROOT, "tests", "cpp", "zstd_core_host.cpp")
 ZSHOST_LIB = os.path.join(ROOT, "tests", "cpp", "_bin", "libzshost.so")
 
 

@@ -398,8 +398,10 @@ hipError_t launch_to_wire(const uint8_t* disk, uint8_t* wire, const rpgpu_batch_
 // rpgpu_stamp (rp_validate.hip): base offset of batch i = next + offs[i]
 // (RPGPU_STAMP_OFFSETS: offs = exclusive scan of the steps), cursor zeroed
 hipError_t launch_stamp_steps(const uint8_t* data, const uint64_t* pos, uint32_t n, uint64_t* steps, hipStream_t s);
+// d_n (optional, device): the batch count is min(*d_n, n)
 hipError_t launch_stamp(uint8_t* data, const uint64_t* pos, const uint32_t* plen, const uint64_t* offs, int64_t next,
-                        uint32_t n, uint32_t flags, const Tables* T, uint32_t* cursor, uint32_t grid, hipStream_t s);
+                        uint32_t n, uint32_t flags, const Tables* T, uint32_t* cursor, uint32_t grid, hipStream_t s,
+                        const uint32_t* d_n = nullptr);
 hipError_t scan_exclusive_u64(uint64_t* data, uint64_t n, void* temp, size_t temp_bytes, hipStream_t s);
 // n = min(*d_n, n_cap), read on the device
 hipError_t scan_exclusive_u64_devn(uint64_t* data, const uint64_t* d_n, uint64_t n_cap, void* temp, hipStream_t s);
@@ -414,5 +416,30 @@ hipError_t launch_segment_index_pieces(const rpgpu_batch_result* batches, uint64
                                        const rpgpu_segment_summary* sums, uint32_t n_segments, uint64_t step,
                                        rpgpu_index_state* states, uint32_t* rel_offset, uint32_t* rel_time,
                                        uint64_t* position, void* ws, hipStream_t s);
+
+
+// rp_compact.hip: key compaction (rpgpu_compact).  Workspace arrays are
+// context scratch; nb / nr bound the source job's batch / record totals.
+struct CompactArgs {
+    rpgpu_compact_job job;
+    uint64_t nb, nr;          // job.batch_capacity / job.record_capacity
+    uint64_t* table;          // key table: tag << 32 | (record slot + 1), 0 = empty
+    uint64_t table_mask;      // words - 1 (a power of two)
+    uint32_t tag_mask;        // ~0u (RPGPU_CKEY_TAG_BITS in the diagnostic build: fewer tag bits)
+    uint32_t* seg_state;      // n_segments: bit 0 not clean, bit 1 offsets
+    uint64_t* seg_acc;        // n_segments * 3: records in, records kept, batches rewritten
+    uint64_t* bpos;           // nb + 1: output bytes per source batch -> exclusive scan
+    uint64_t* bcnt;           // nb + 1: 1 per source batch with kept records -> exclusive scan
+    uint32_t* bkept;          // nb: kept records per source batch
+    uint32_t* bplen;          // nb: output payload bytes per source batch
+    uint64_t* spos;           // nb: rpgpu_stamp positions of the output batches
+    uint32_t* splen;          // nb: their payload lengths
+    uint32_t* counters;       // [0] key compare mismatches, [1] batches to stamp, [2] k_stamp's claim cursor
+};
+hipError_t launch_compact_insert(const CompactArgs& a, uint32_t cus, hipStream_t s);  // eligibility + key insert
+hipError_t launch_compact_keep(const CompactArgs& a, uint32_t cus, hipStream_t s);
+hipError_t launch_compact_size(const CompactArgs& a, uint32_t cus, hipStream_t s);
+hipError_t launch_compact_plan(const CompactArgs& a, hipStream_t s);  // after the scans: segments, totals, overflow
+hipError_t launch_compact_write(const CompactArgs& a, uint32_t cus, hipStream_t s);
 
 }  // namespace rp

@@ -132,6 +132,12 @@ struct rpgpu_ctx {
     // rpgpu_segment_index workspace (piece tables), grow-only
     void* iws = nullptr;
     size_t iws_bytes = 0;
+    // rpgpu_compact workspace (key table, per-batch plan, scan temporaries), grow-only;
+    // its stage events (rpgpu_set_timing)
+    void* cws = nullptr;
+    size_t cws_bytes = 0;
+    hipEvent_t cev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool cev_live = false;
     // k_lz_exec parse records (kRecsPerLane per lane of each resident wave),
     // allocated on the first decode job
     SeqRec* seqs = nullptr;
@@ -323,6 +329,9 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     if (c->ws) hipFree(c->ws);
     if (c->uws) hipFree(c->uws);
     if (c->iws) hipFree(c->iws);
+    if (c->cws) hipFree(c->cws);
+    for (hipEvent_t e : c->cev)
+        if (e) hipEventDestroy(e);
     if (c->qws) hipFree(c->qws);
     if (c->sws) hipFree(c->sws);
     if (c->bd) hipFree(c->bd);
@@ -1392,6 +1401,125 @@ int rpgpu_stamp(rpgpu_ctx* c, uint8_t* d_data, const uint64_t* d_pos, const uint
     }
     HIPCHK(c, launch_stamp(d_data, d_pos, d_payload_len, steps, next_offset, n, flags, c->d_tables, cursor, c->cu_count, s));
     return ws_release(c, s);
+}
+
+// Key compaction over a completed job's outputs (kernels in rp_compact.hip).
+size_t rpgpu_compact_sizeof(int which) {
+    switch (which) {
+    case 0: return sizeof(rpgpu_compact_batch);
+    case 1: return sizeof(rpgpu_compact_segment);
+    case 2: return sizeof(rpgpu_compact_totals);
+    case 3: return sizeof(rpgpu_compact_job);
+    default: return 0;
+    }
+}
+
+int rpgpu_compact(rpgpu_ctx* c, const rpgpu_compact_job* job, void* stream) {
+    if (!c || !job) return RPGPU_E_INVALID;
+    if (!job->d_totals || !job->d_ctotals || !job->d_out_seg_offsets)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_compact: missing argument");
+    if (job->n_segments && (!job->d_seg_offsets || !job->d_summaries || !job->d_seg))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_compact: missing segment arrays");
+    if ((job->batch_capacity && (!job->d_batches || !job->d_data)) || (job->record_capacity && (!job->d_records || !job->d_keep)))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_compact: missing job outputs");
+    if ((job->out_capacity && !job->d_out) || (job->out_batch_capacity && !job->d_out_batches))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_compact: missing output buffer");
+    if (((uintptr_t)job->d_out & 15) != 0) return fail(c, RPGPU_E_INVALID, "rpgpu_compact: d_out must be 16-byte aligned");
+    if (job->record_capacity >= 0xFFFFFFFFull || job->batch_capacity >= 0xFFFFFFFFull || job->n_segments > 0x7FFFFFFFu)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_compact: capacity out of range");
+    hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    const uint64_t nb = job->batch_capacity, nr = job->record_capacity, nseg = job->n_segments;
+    uint64_t words = 64;
+    while (words < 2 * nr) words <<= 1;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t o = need; need += align_up(bytes, 256); return o; };
+    const size_t o_table = take(words * 8), o_state = take(nseg * 4), o_acc = take(nseg * 24);
+    const size_t o_bpos = take((nb + 1) * 8), o_bcnt = take((nb + 1) * 8), o_bkept = take(nb * 4), o_bplen = take(nb * 4);
+    const size_t o_spos = take(nb * 8), o_splen = take(nb * 4), o_scan = take(scan_temp_bytes(nb) + 64), o_cnt = take(256);
+    need += 256;
+    if (need > c->cws_bytes) {
+        if (c->cws) {
+            if (int rc = ws_drain(c, s)) return rc;
+            HIPCHK(c, hipFree(c->cws));
+            c->cws = nullptr;
+            c->cws_bytes = 0;
+        }
+        if (hipMalloc(&c->cws, need) != hipSuccess) { c->cws = nullptr; return fail(c, RPGPU_E_NOMEM, "rpgpu_compact workspace"); }
+        c->cws_bytes = need;
+    }
+    if (int rc = ws_acquire(c, s)) return rc;
+    uint8_t* w = (uint8_t*)c->cws;
+    CompactArgs a;
+    a.job = *job;
+    a.nb = nb;
+    a.nr = nr;
+    a.table = (uint64_t*)(w + o_table);
+    a.table_mask = words - 1;
+    a.tag_mask = ~0u;
+    // RPGPU_CKEY_TAG_BITS=n (diagnostic build): n tag bits, and probes start at the tag, so that
+    // different keys meet on one tag
+    if (const char* e = diag_env("RPGPU_CKEY_TAG_BITS")) {
+        const int bits = atoi(e);
+        if (bits >= 0 && bits < 32) a.tag_mask = (1u << bits) - 1u;
+    }
+    a.seg_state = (uint32_t*)(w + o_state);
+    a.seg_acc = (uint64_t*)(w + o_acc);
+    a.bpos = (uint64_t*)(w + o_bpos);
+    a.bcnt = (uint64_t*)(w + o_bcnt);
+    a.bkept = (uint32_t*)(w + o_bkept);
+    a.bplen = (uint32_t*)(w + o_bplen);
+    a.spos = (uint64_t*)(w + o_spos);
+    a.splen = (uint32_t*)(w + o_splen);
+    a.counters = (uint32_t*)(w + o_cnt);
+    const bool timed = c->timing;
+    auto mark = [&](int i) -> hipError_t {
+        if (!timed) return hipSuccess;
+        if (!c->cev[i]) {
+            hipError_t e = hipEventCreate(&c->cev[i]);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(c->cev[i], s);
+    };
+    c->cev_live = false;
+    HIPCHK(c, mark(0));
+    HIPCHK(c, hipMemsetAsync(a.table, 0, words * 8, s));
+    HIPCHK(c, hipMemsetAsync(a.counters, 0, 256, s));
+    HIPCHK(c, hipMemsetAsync(a.bpos, 0, 8, s));
+    HIPCHK(c, hipMemsetAsync(a.bcnt, 0, 8, s));
+    if (nr) HIPCHK(c, hipMemsetAsync(job->d_keep, 0, (nr + 63) / 64 * 8, s));
+    HIPCHK(c, hipMemsetAsync(job->d_ctotals, 0, sizeof(rpgpu_compact_totals), s));
+    HIPCHK(c, launch_compact_insert(a, c->cu_count, s));
+    HIPCHK(c, mark(1));
+    HIPCHK(c, launch_compact_keep(a, c->cu_count, s));
+    HIPCHK(c, mark(2));
+    HIPCHK(c, launch_compact_size(a, c->cu_count, s));
+    if (nb) {
+        HIPCHK(c, scan_exclusive_u64(a.bpos, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+        HIPCHK(c, scan_exclusive_u64(a.bcnt, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+    }
+    HIPCHK(c, launch_compact_plan(a, s));
+    HIPCHK(c, mark(3));
+    HIPCHK(c, launch_compact_write(a, c->cu_count, s));
+    HIPCHK(c, mark(4));
+    const uint64_t nstamp = std::min<uint64_t>(nb, job->out_batch_capacity);
+    if (nstamp)
+        HIPCHK(c, launch_stamp(job->d_out, a.spos, a.splen, nullptr, 0, (uint32_t)nstamp, RPGPU_STAMP_CRC, c->d_tables,
+                               a.counters + 2, c->cu_count, s, a.counters + 1));
+    HIPCHK(c, mark(5));
+    c->cev_live = timed;
+    return ws_release(c, s);
+}
+
+int rpgpu_compact_timings(rpgpu_ctx* c, float* ms, int n) {
+    if (!c || !ms) return RPGPU_E_INVALID;
+    if (!c->cev_live) return fail(c, RPGPU_E_INVALID, "rpgpu_compact_timings: no timed rpgpu_compact");
+    HIPCHK(c, hipEventSynchronize(c->cev[5]));
+    float v[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventElapsedTime(&v[0], c->cev[0], c->cev[5]));
+    for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->cev[i - 1], c->cev[i]));
+    for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
+    return RPGPU_OK;
 }
 
 // kafka::writer_serialize_batch over batches [first, first + n) of a

@@ -1721,8 +1721,14 @@ DEV uint32_t be40_src(uint32_t k) {
 __global__ __launch_bounds__(1024) void k_stamp(uint8_t* data, const uint64_t* __restrict__ pos,
                                                 const uint32_t* __restrict__ plen,
                                                 const uint64_t* __restrict__ offs, int64_t next, uint32_t n,
-                                                uint32_t flags, const Tables* T, uint32_t* cursor) {
+                                                uint32_t flags, const Tables* T, uint32_t* cursor,
+                                                const uint32_t* __restrict__ d_n) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    if (d_n) {  // the count lives on the device (rpgpu_compact)
+        const uint32_t m = uni32(*d_n);
+        n = m < n ? m : n;
+        if (n == 0) return;
+    }
     init_lds_tables(lds, T);
     const uint32_t l = lane_v();
     const Keys K = make_keys();
@@ -1786,14 +1792,15 @@ hipError_t launch_stamp_steps(const uint8_t* data, const uint64_t* pos, uint32_t
 }
 
 hipError_t launch_stamp(uint8_t* data, const uint64_t* pos, const uint32_t* plen, const uint64_t* offs, int64_t next,
-                        uint32_t n, uint32_t flags, const Tables* T, uint32_t* cursor, uint32_t grid, hipStream_t s) {
+                        uint32_t n, uint32_t flags, const Tables* T, uint32_t* cursor, uint32_t grid, hipStream_t s,
+                        const uint32_t* d_n) {
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)k_stamp, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsValidateBytes);
         attr = true;
     }
     hipLaunchKernelGGL(k_stamp, dim3(grid), dim3(64 * kVWaves), kLdsValidateBytes, s, data, pos, plen, offs, next, n,
-                       flags, T, cursor);
+                       flags, T, cursor, d_n);
     return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from ._lib import CapacityC, JobC, RpgpuError, check, load
+from ._lib import CapacityC, CompactJobC, JobC, RpgpuError, check, load
 
 
 def _torch():
@@ -55,6 +55,46 @@ class HostResult:
     summaries: np.ndarray
     totals: np.void
     bitmap: np.ndarray
+
+
+@dataclass
+class CompactResult:
+    """Device outputs of Engine.compact (rpgpu_compact)."""
+    keep: "object"             # int64 tensor: bit i of the bitmap = record-index slot i survives
+    out: "object"              # uint8 tensor: the compacted segments back to back
+    out_seg_offsets: "object"  # int64 tensor, n_segments + 1
+    batches: "object"          # uint8 tensor viewed as abi.COMPACT_BATCH on the host
+    segments: "object"
+    totals: "object"
+    n_segments: int
+    n_records: int
+
+    def totals_host(self):
+        return np.frombuffer(self.totals.cpu().numpy().tobytes(), dtype=abi.COMPACT_TOTALS)[0]
+
+    def to_host(self):
+        t = self.totals_host()
+        ok = not t["overflow"]
+        nb = int(t["batches_out"]) if ok else 0
+        nby = int(t["bytes_out"]) if ok else 0
+        return HostCompactResult(
+            keep=self.keep.cpu().numpy().view(np.uint64)[: (self.n_records + 63) // 64],
+            out=self.out[:nby].cpu().numpy(),
+            out_seg_offsets=self.out_seg_offsets.cpu().numpy().view(np.uint64),
+            batches=np.frombuffer(self.batches[: nb * abi.COMPACT_BATCH.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.COMPACT_BATCH),
+            segments=np.frombuffer(self.segments.cpu().numpy().tobytes(), dtype=abi.COMPACT_SEGMENT)[: self.n_segments],
+            totals=t)
+
+
+@dataclass
+class HostCompactResult:
+    keep: np.ndarray
+    out: np.ndarray
+    out_seg_offsets: np.ndarray
+    batches: np.ndarray
+    segments: np.ndarray
+    totals: np.void
 
 
 class Engine:
@@ -343,6 +383,84 @@ class Engine:
                                          C.c_void_p(s.cuda_stream)), self.ctx, "rpgpu_segment_index")
         finish(out.batches, out.summaries, states, rel_off, rel_time, pos)
         return states, rel_off, rel_time, pos
+
+    def compact(self, data, seg_offsets, out: DeviceResult, stream=None, out_capacity: int = None,
+                out_batch_capacity: int = None, sync: bool = True, out_buffer=None) -> "CompactResult":
+        """rpgpu_compact: key compaction of every segment of a completed
+        disk-layout job `out` (JOB_CRC | JOB_PARSE | JOB_DECODE over `data`,
+        a torch uint8 CUDA tensor): which records survive, and the compacted
+        segments (copy_data_segment_reducer::filter's batches, headers
+        stamped).  Returns device tensors; .to_host() gives numpy views.
+        The output capacities default to what always fits; a call whose
+        capacity turns out too small is retried once with the sizes the
+        device reported (sync=False skips that check and the retry).
+        out_buffer: a uint8 CUDA tensor of at least out_capacity bytes to
+        write the first attempt into."""
+        torch = _torch()
+        dev = data.device
+        t = out.totals_host()
+        nb = int(min(t["n_batches"], out.batches.numel() // abi.BATCH_RESULT.itemsize))
+        nr = int(min(t["n_records"], out.records.numel() // abi.RECORD_INDEX.itemsize))
+        nseg = out.n_segments
+        h_off = np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.uint64))
+        d_off = torch.from_numpy(h_off.view(np.int64)).to(dev)
+        if out_capacity is None:
+            b = np.frombuffer(out.batches[: nb * abi.BATCH_RESULT.itemsize].cpu().numpy().tobytes(), dtype=abi.BATCH_RESULT)
+            out_capacity = int(np.sum(b["decoded_len"].astype(np.int64))) + abi.HEADER_SIZE * nb + 16
+        if out_batch_capacity is None:
+            out_batch_capacity = nb
+        u8 = torch.uint8
+        keep = torch.empty(max((nr + 63) // 64, 1), dtype=torch.int64, device=dev)
+        seg_off = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+        segs = torch.zeros(max(nseg, 1) * abi.COMPACT_SEGMENT.itemsize, dtype=u8, device=dev)
+        tot = torch.zeros(abi.COMPACT_TOTALS.itemsize, dtype=u8, device=dev)
+        for attempt in range(2):
+            if out_buffer is not None and attempt == 0:
+                if out_buffer.numel() < out_capacity:
+                    raise RpgpuError("compact: out_buffer smaller than out_capacity")
+                obuf = out_buffer
+            else:
+                obuf = torch.zeros(max(out_capacity, 16), dtype=u8, device=dev)
+            obat = torch.zeros(max(out_batch_capacity, 1) * abi.COMPACT_BATCH.itemsize, dtype=u8, device=dev)
+            job = CompactJobC()
+            job.d_data = data.data_ptr()
+            job.d_seg_offsets = d_off.data_ptr()
+            job.n_segments = nseg
+            job.d_batches = out.batches.data_ptr()
+            job.batch_capacity = nb
+            job.d_records = out.records.data_ptr()
+            job.record_capacity = nr
+            job.d_decoded = out.decoded.data_ptr()
+            job.d_summaries = out.summaries.data_ptr()
+            job.d_totals = out.totals.data_ptr()
+            job.d_keep = keep.data_ptr()
+            job.d_out = obuf.data_ptr()
+            job.out_capacity = out_capacity
+            job.d_out_seg_offsets = seg_off.data_ptr()
+            job.d_out_batches = obat.data_ptr()
+            job.out_batch_capacity = out_batch_capacity
+            job.d_seg = segs.data_ptr()
+            job.d_ctotals = tot.data_ptr()
+            s, finish = self._stream(dev, stream)
+            check(self.L.rpgpu_compact(self.ctx, C.byref(job), C.c_void_p(s.cuda_stream)), self.ctx, "rpgpu_compact")
+            finish(data, d_off, out.batches, out.records, out.decoded, out.summaries, out.totals, keep, obuf, seg_off,
+                   obat, segs, tot)
+            res = CompactResult(keep, obuf, seg_off, obat, segs, tot, nseg, nr)
+            if not sync:
+                return res
+            s.synchronize()
+            ct = res.totals_host()
+            if not ct["overflow"] or attempt:
+                return res
+            out_capacity = int(ct["out_capacity_needed"])
+            out_batch_capacity = int(ct["out_batch_capacity_needed"])
+        return res
+
+    def compact_timings(self):
+        """Device milliseconds of the last rpgpu_compact run under set_timing()."""
+        ms = (C.c_float * 6)()
+        check(self.L.rpgpu_compact_timings(self.ctx, ms, 6), self.ctx, "rpgpu_compact_timings")
+        return {"total": ms[0], "insert": ms[1], "keep": ms[2], "size_scan": ms[3], "write": ms[4], "stamp": ms[5]}
 
     @staticmethod
     def index_to_host(states, rel_off, rel_time, pos, n_segments: int):

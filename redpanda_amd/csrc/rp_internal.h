@@ -329,7 +329,7 @@ hipError_t launch_discover(const DeviceJob& j, hipStream_t s);
 hipError_t launch_resolve(const DeviceJob& j, hipStream_t s);
 hipError_t launch_emit(const DeviceJob& j, hipStream_t s);
 hipError_t launch_validate(const DeviceJob& j, hipStream_t s, uint32_t grid, bool compose = true);  // rp_validate.hip
-hipError_t launch_crc_compose(const DeviceJob& j, hipStream_t s, uint32_t grid, uint32_t waves = 16);
+hipError_t launch_crc_compose(const DeviceJob& j, hipStream_t s, uint32_t grid);
 bool dchain_wanted(const DeviceJob& j);                                         // rp_validate.hip
 hipError_t launch_dchain(const DeviceJob& j, hipStream_t s, uint32_t grid);
 hipError_t launch_validate_decoded(const DeviceJob& j, hipStream_t s, uint32_t grid);
@@ -350,7 +350,7 @@ hipError_t launch_inflate(const DeviceJob& j, hipStream_t s, uint32_t grid);
 hipError_t launch_zparse(const DeviceJob& j, hipStream_t s, uint32_t grid);
 hipError_t launch_zplan(const DeviceJob& j, hipStream_t s, uint32_t grid);
 hipError_t launch_gzsplan(const DeviceJob& j, hipStream_t s);
-hipError_t launch_gzsplit(const DeviceJob& j, hipStream_t s, uint32_t grid, int part = 0);  // part 1: find, 2: decode + resolve, 0: all
+hipError_t launch_gzsplit(const DeviceJob& j, hipStream_t s, uint32_t grid, int part);  // part 1: find, 2: decode + resolve
 hipError_t launch_zfallback(const DeviceJob& j, hipStream_t s, uint32_t grid);
 hipError_t launch_zexact(const DeviceJob& j, hipStream_t s, int pass);  // rp_inflate.hip
 hipError_t launch_zstamps(hipStream_t s, int print);  // RPGPU_ZSTAMPS builds: reset / print the decoder stamps

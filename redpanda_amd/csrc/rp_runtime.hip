@@ -94,6 +94,28 @@ static const Tables* host_tables() {
     return T;
 }
 
+// A grow-only buffer the context owns, in device or pinned host memory:
+// grow() (below) is the only place one is allocated or replaced, release()
+// the only place one is freed.
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+    template <class T>
+    T* as() const { return (T*)p; }
+    void release() {
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// a side stream of a job and the events of its fork and join (Fork, below)
+struct Side {
+    hipStream_t stream = nullptr;
+    hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+};
+
 }  // namespace rp
 
 using namespace rp;
@@ -102,53 +124,32 @@ struct rpgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     Tables* d_tables = nullptr;
-    // growable device workspace
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
-    // pinned staging for small host->device uploads
-    void* pin = nullptr;
-    size_t pin_bytes = 0;
+    Buf ws;  // the submit pipeline's device workspace
     bool timing = false;
     // one event set per timed submit: start, discover done, plan done,
     // decode done, validate done, walk done, end; resolved lazily by
     // rpgpu_last_timings
     std::vector<std::array<hipEvent_t, 7>> ev_sets;
-    // rpgpu_uncompress staging (device)
-    void* uws = nullptr;
-    size_t uws_bytes = 0;
     size_t ev_used = 0;
     uint32_t cu_count = 256;
-    // rpgpu_query_capacity scratch (summaries, totals, batch results), grow-only
-    void* qws = nullptr;
-    size_t qws_bytes = 0;
-    // rpgpu_uncompress_batch staging: pinned host and device, grow-only
-    void* bh = nullptr;
-    size_t bh_bytes = 0;
-    void* bd = nullptr;
-    size_t bd_bytes = 0;
-    // rpgpu_stamp workspace (offset steps, scan temporaries, claim cursor)
-    void* sws = nullptr;
-    size_t sws_bytes = 0;
-    // rpgpu_segment_index workspace (piece tables), grow-only
-    void* iws = nullptr;
-    size_t iws_bytes = 0;
-    // rpgpu_compact workspace (key table, per-batch plan, scan temporaries), grow-only;
+    Buf uws;                       // rpgpu_uncompress staging (device)
+    Buf qws;                       // rpgpu_query_capacity scratch (summaries, totals, batch results)
+    Buf bh{nullptr, 0, true}, bd;  // rpgpu_uncompress_batch / rpgpu_compress_batch staging: pinned host and device
+    Buf sws;                       // rpgpu_stamp workspace (offset steps, scan temporaries, claim cursor)
+    Buf iws;                       // rpgpu_segment_index workspace (piece tables)
+    // rpgpu_compact workspace (key table, per-batch plan, scan temporaries);
     // its stage events (rpgpu_set_timing)
-    void* cws = nullptr;
-    size_t cws_bytes = 0;
+    Buf cws;
     hipEvent_t cev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool cev_live = false;
     // k_lz_exec parse records (kRecsPerLane per lane of each resident wave),
     // allocated on the first decode job
-    SeqRec* seqs = nullptr;
+    Buf seqs;
     uint32_t exec_waves = 0;
-    // k_lz_walk record pool (slabs) and its chain links, grow-only
-    void* pool = nullptr;
-    size_t pool_bytes = 0;
+    Buf pool;  // k_lz_walk record pool (slabs) and its chain links
     // k_lzf_walk's 8-byte records (independent-block fast path); without it
     // every piece takes the walk / exec kernels
-    void* fpool = nullptr;
-    size_t fpool_bytes = 0;
+    Buf fpool;
     std::string err;
     // Context scratch (ws, pool, seqs, sws, iws) is shared by every job on
     // the context, whichever stream it is launched on: each async entry
@@ -161,58 +162,31 @@ struct rpgpu_ctx {
     // bytes in, per-batch results out), used alternately so the H2D copy of
     // group g + 1 runs while group g validates
     hipStream_t copy = nullptr;
-    // the zstd members' first pass (k_zparse) runs on a side stream beside
-    // k_members_first's gzip members: forked after k_emit, joined before the
-    // slot scans
-    hipStream_t side = nullptr;
-    hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-    hipStream_t side2 = nullptr;  // k_raw_copy beside k_lzf_walk and k_lz_walk; the gzip members
-                                  // the split decode does not plan, beside it
-    hipEvent_t join2_ev = nullptr, mfork_ev = nullptr, mjoin_ev = nullptr;
+    // the zstd members' first pass (k_zparse) beside k_members_first's gzip
+    // members, the listed LZ4 blocks (k_lzf_walk) beside k_lz_walk, the LZ4F
+    // content checksums beside k_decode_finish
+    Side side;
+    // k_raw_copy beside k_lzf_walk and k_lz_walk; the gzip members the split
+    // decode does not plan, beside it
+    Side side2;
     struct HostSlot {
-        uint8_t* d_data = nullptr;
-        uint64_t data_bytes = 0;
-        uint64_t* d_offs = nullptr;
-        uint64_t offs_n = 0;
-        rpgpu_batch_result* d_batches = nullptr;
-        uint64_t bcap = 0;
-        rpgpu_record_index* d_records = nullptr;
-        uint64_t rcap = 0;
-        uint8_t* d_decoded = nullptr;
-        uint64_t dcap = 0;
-        rpgpu_segment_summary* d_sums = nullptr;
-        uint64_t sums_n = 0;
-        rpgpu_job_totals* d_tot = nullptr;
-        rpgpu_job_totals* h_tot = nullptr;  // pinned
+        // device staging, in elements of the named type
+        Buf d_data, d_offs, d_batches, d_records, d_decoded, d_sums, d_tot;
+        Buf h_tot{nullptr, 0, true};
         // segment index rebuild (rpgpu_host_job.index_step)
-        rpgpu_index_state* d_ist = nullptr;
-        uint64_t ist_n = 0;
-        uint32_t* d_ro = nullptr;
-        uint32_t* d_rt = nullptr;
-        uint64_t* d_ps = nullptr;
-        uint64_t ix_n = 0;
+        Buf d_ist, d_ro, d_rt, d_ps;
         hipEvent_t h2d = nullptr, done = nullptr;
         std::vector<uint64_t> h_offs;
         std::vector<rpgpu_index_state> h_ist;
     } hs[2];
-    // rpgpu_stamp_host staging (pinned host + device), grow-only
-    void* sth = nullptr;
-    size_t sth_bytes = 0;
-    void* std_ = nullptr;
-    size_t std_bytes = 0;
+    Buf sth{nullptr, 0, true}, std_;  // rpgpu_stamp_host staging (pinned host + device)
     // RPGPU_JOB_HOST_CODECS: the host step's items and staging (device and
-    // pinned host, grow-only); hc_n = items of the job being enqueued
-    struct Grow {
-        void* p = nullptr;
-        size_t bytes = 0;
-        bool pinned = false;
-    } hc_items, hc_items_h, hc_in, hc_in_h, hc_out, hc_out_h, hc_small;
+    // pinned host); hc_n = items of the job being enqueued
+    Buf hc_items, hc_items_h{nullptr, 0, true}, hc_in, hc_in_h{nullptr, 0, true}, hc_out, hc_out_h{nullptr, 0, true},
+        hc_small{nullptr, 0, true};
     uint32_t hc_n = 0;
-    // gzip / zstd first-pass output pool (k_members_first), grow-only
-    void* gz_pool = nullptr;
-    size_t gz_pool_bytes = 0;
-    void* gzs_pool = nullptr;  // the gzip split decode's chunk symbols
-    size_t gzs_pool_bytes = 0;
+    Buf gz_pool;   // gzip / zstd first-pass output pool (k_members_first)
+    Buf gzs_pool;  // the gzip split decode's chunk symbols
 };
 
 namespace {
@@ -254,30 +228,178 @@ int ws_drain(rpgpu_ctx* c, hipStream_t s) {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Environment overrides exist in the diagnostic build only
-// (librpgpu_diag.so, -DRPGPU_DIAG, loaded with RPGPU_VARIANT=diag): the
-// product library reads no environment.
-#ifdef RPGPU_DIAG
-const char* diag_env(const char* name) { return getenv(name); }
+// Grow `b` to at least `want` bytes (never shrinks).  The buffer may still be
+// in use by earlier work on the context, on any stream, so that work is
+// drained before the old buffer is freed.  On failure `b` is left empty.
+int grow(rpgpu_ctx* c, Buf& b, size_t want, hipStream_t s, const char* what) {
+    if (want <= b.bytes) return RPGPU_OK;
+    if (b.p) {
+        if (int rc = ws_drain(c, s)) return rc;
+        b.release();
+    }
+    if ((b.pinned ? hipHostMalloc(&b.p, want, hipHostMallocDefault) : hipMalloc(&b.p, want)) != hipSuccess) {
+        b.p = nullptr;
+        return fail(c, RPGPU_E_NOMEM, what);
+    }
+    b.bytes = want;
+    return RPGPU_OK;
+}
+
+// A pool the job can do without (fpool, gz_pool, gzs_pool): failing to get it
+// is not an error, the job takes its fallback path with the same results.
+int grow_optional(rpgpu_ctx* c, Buf& b, size_t want, hipStream_t s) {
+    const int rc = grow(c, b, want, s, "");
+    if (rc != RPGPU_E_NOMEM) return rc;
+    (void)hipGetLastError();
+    c->err.clear();
+    return RPGPU_OK;
+}
+
+// The context scratch for the length of one job: the stream waits for the
+// previous job on construction and records this job's end on every way out.
+// release() is the success path (its status is the job's); after an error
+// return the destructor records the event and the job's own error stands.
+class ScratchScope {
+    rpgpu_ctx* c_;
+    hipStream_t s_;
+    int rc_;
+
+  public:
+    ScratchScope(rpgpu_ctx* c, hipStream_t s) : c_(c), s_(s), rc_(ws_acquire(c, s)) {}
+    ScratchScope(const ScratchScope&) = delete;
+    int acquired() { return rc_; }  // not RPGPU_OK: nothing is held, return it
+    int release() {
+        rc_ = -1;
+        return ws_release(c_, s_);
+    }
+    ~ScratchScope() {
+        if (rc_ != RPGPU_OK) return;
+        const std::string own = c_->err;
+        (void)ws_release(c_, s_);
+        c_->err = own;
+    }
+};
+
+// Everything the diagnostic build (librpgpu_diag.so, -DRPGPU_DIAG, loaded
+// with RPGPU_VARIANT=diag) can change, read from the environment once, on
+// first use.  The product library reads no environment: there diag() is the
+// defaults below, a constant.
+struct Diag {
+    bool debug_sync = false;          // RPGPU_DEBUG_SYNC=1: synchronize after every stage and name the one that failed
+    uint64_t split_min = 0;           // RPGPU_SPLIT_MIN_KIB=n: the split-CRC threshold, at least 64 bytes (0: from the job)
+    uint32_t pool_slabs = ~0u;        // RPGPU_POOL_SLABS=n: at most n record-pool slabs (k_lz_exec walks what is cut short)
+    bool crc_compose = true;          // RPGPU_CRC_COMPOSE=0: k_validate streams every stored payload
+    bool dchain = true;               // RPGPU_DCHAIN=0: k_validate_decoded chains the records itself
+    bool lzf = true;                  // RPGPU_LZF=0: every LZ4 piece through the walk / exec kernels
+    uint64_t frec_cap = ~0ull;        // RPGPU_FREC_CAP=n: at most n fast-path records (listed groups mix with walked ones)
+    size_t inf_pool = 0;              // RPGPU_INF_POOL_KIB=n: the gzip / zstd first-pass pool, at least 4 KiB (0: from the job)
+    uint32_t zs_fast = 1;             // RPGPU_ZS_FAST=0: every zstd member through the wave decoder
+#ifdef RPGPU_NO_GZS                   // A/B variant (scripts/build_exp.py): every gzip member serial
+    bool gzs = false;
 #else
-const char* diag_env(const char*) { return nullptr; }
+    bool gzs = true;                  // RPGPU_GZS=0: every gzip member serial
+#endif
+    bool xxh_side = true;             // RPGPU_XXH_SIDE=0: the content checksums inside k_decode_finish
+    uint32_t lzwalk_wgs = 0;          // RPGPU_LZWALK_WGS=n: k_lz_walk's grid in workgroups (0: 16 per CU)
+    uint32_t walk_wgs = 8;            // RPGPU_WALK_WGS=n: k_walk's workgroups per CU
+    bool host_codec_missing = false;  // RPGPU_HOST_CODEC_MISSING=1: act as if libzstd could not be loaded
+    bool index_serial = false;        // RPGPU_INDEX_SERIAL=1: the one-wave-per-segment index walk
+    uint32_t ckey_tag_mask = ~0u;     // RPGPU_CKEY_TAG_BITS=n: n tag bits in the compaction key table
+};
+#ifdef RPGPU_DIAG
+Diag diag_from_env() {
+    Diag d;
+    auto diag_env = [](const char* name) { return getenv(name); };
+    auto is = [&](const char* name, char v) { const char* e = diag_env(name); return e && *e == v; };
+    d.debug_sync = is("RPGPU_DEBUG_SYNC", '1');
+    if (const char* e = diag_env("RPGPU_SPLIT_MIN_KIB")) d.split_min = std::max<uint64_t>(strtoull(e, nullptr, 10) << 10, 64);
+    if (const char* e = diag_env("RPGPU_POOL_SLABS")) d.pool_slabs = (uint32_t)atoi(e);
+    d.crc_compose = !is("RPGPU_CRC_COMPOSE", '0');
+    d.dchain = !is("RPGPU_DCHAIN", '0');
+    d.lzf = !is("RPGPU_LZF", '0');
+    if (const char* e = diag_env("RPGPU_FREC_CAP")) d.frec_cap = strtoull(e, nullptr, 10);
+    if (const char* e = diag_env("RPGPU_INF_POOL_KIB")) d.inf_pool = std::max<size_t>(strtoull(e, nullptr, 10) << 10, 4096);
+    d.zs_fast = is("RPGPU_ZS_FAST", '0') ? 0u : 1u;
+    if (is("RPGPU_GZS", '0')) d.gzs = false;
+    d.xxh_side = !is("RPGPU_XXH_SIDE", '0');
+    if (const char* e = diag_env("RPGPU_LZWALK_WGS")) d.lzwalk_wgs = (uint32_t)atoi(e);
+    if (const char* e = diag_env("RPGPU_WALK_WGS")) d.walk_wgs = (uint32_t)atoi(e);
+    d.host_codec_missing = is("RPGPU_HOST_CODEC_MISSING", '1');
+    d.index_serial = is("RPGPU_INDEX_SERIAL", '1');
+    if (const char* e = diag_env("RPGPU_CKEY_TAG_BITS")) {
+        // probes start at the tag, so that different keys meet on one tag
+        const int bits = atoi(e);
+        if (bits >= 0 && bits < 32) d.ckey_tag_mask = (1u << bits) - 1u;
+    }
+    return d;
+}
+const Diag& diag() {
+    static const Diag d = diag_from_env();
+    return d;
+}
+#else
+constexpr Diag kNoDiag{};
+constexpr const Diag& diag() { return kNoDiag; }
 #endif
 
-// The side stream of a job (the zstd member pass beside the gzip one, the LZ4
-// lane walk beside the raw copies and the other pieces' walk): created at the
-// device's highest stream priority.  HIP spreads a process's streams over
-// GPU_MAX_HW_QUEUES hardware queues (4 here) round robin, and a side stream
-// that lands on the caller's queue runs after it instead of beside it (C6's
-// member pass measured 64 ms alone, 77 ms after the bench's H2D stanza had
-// created its copy streams); a priority of its own gives it a queue of its own.
-// RPGPU_SIDE_PRIO=0 (diagnostic build): the default priority (A/B).
+// A side stream is created at the device's highest stream priority.  HIP
+// spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (4 here)
+// round robin, and a side stream that lands on the caller's queue runs after
+// it instead of beside it (C6's member pass measured 64 ms alone, 77 ms after
+// the bench's H2D stanza had created its copy streams); a priority of its own
+// gives it a queue of its own.  (The default priority was measured on the
+// raw-copy stream and lost: DESIGN.md §5.)
 hipError_t side_stream_create(hipStream_t* out) {
-    static const bool prio = [] { const char* e = diag_env("RPGPU_SIDE_PRIO"); return !(e && *e == '0'); }();
     int least = 0, greatest = 0;
-    if (prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
         return hipStreamCreateWithPriority(out, hipStreamNonBlocking, greatest);
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
+
+// One fork of a job's stream `s` onto a side stream of the context: open()
+// makes the side stream (created on first use, with its two events) wait for
+// what `s` holds now, join() makes `s` wait for what the side stream holds
+// then (or held at end(), where the caller marked the side stream's part
+// complete as soon as it was enqueued).  The destructor joins if join() was
+// not reached, so that an error return still orders `s`, where the scratch is
+// released, after the side stream's kernels.
+class Fork {
+    hipStream_t s_ = nullptr;
+    Side* side_ = nullptr;
+    bool ended_ = false;
+
+  public:
+    Fork() = default;
+    Fork(const Fork&) = delete;
+    ~Fork() { (void)join(); }
+    // at: an open fork of the same stream with nothing enqueued on `s` since;
+    // this one then forks at the same point (it waits for that fork's event)
+    hipError_t open(hipStream_t s, Side& sd, const Fork* at = nullptr) {
+        hipError_t e = sd.stream ? hipSuccess : side_stream_create(&sd.stream);
+        if (e == hipSuccess && !sd.fork_ev) e = hipEventCreateWithFlags(&sd.fork_ev, hipEventDisableTiming);
+        if (e == hipSuccess && !sd.join_ev) e = hipEventCreateWithFlags(&sd.join_ev, hipEventDisableTiming);
+        if (e == hipSuccess && !at) e = hipEventRecord(sd.fork_ev, s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(sd.stream, at ? at->side_->fork_ev : sd.fork_ev, 0);
+        if (e == hipSuccess) {
+            s_ = s;
+            side_ = &sd;
+        }
+        return e;
+    }
+    // the side stream's part is enqueued: its end is recorded now, join() waits for it
+    hipError_t end() {
+        const hipError_t e = hipEventRecord(side_->join_ev, side_->stream);
+        ended_ = e == hipSuccess;
+        return e;
+    }
+    hipError_t join() {  // nothing to do when the fork was never opened
+        if (!side_) return hipSuccess;
+        Side* sd = side_;
+        side_ = nullptr;
+        const hipError_t e = ended_ ? hipSuccess : hipEventRecord(sd->join_ev, sd->stream);
+        return e == hipSuccess ? hipStreamWaitEvent(s_, sd->join_ev, 0) : e;
+    }
+};
 
 // gzip / zstd: the CPU fallback behind compressor::uncompress (rp_hostcodec.cpp)
 int host_codec(rpgpu_ctx* c, int codec, const void* in, size_t n, void* out, size_t cap, size_t* out_len) {
@@ -326,48 +448,30 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->ws_live) (void)hipEventSynchronize(c->ws_ev);
-    if (c->ws) hipFree(c->ws);
-    if (c->uws) hipFree(c->uws);
-    if (c->iws) hipFree(c->iws);
-    if (c->cws) hipFree(c->cws);
-    for (hipEvent_t e : c->cev)
-        if (e) hipEventDestroy(e);
-    if (c->qws) hipFree(c->qws);
-    if (c->sws) hipFree(c->sws);
-    if (c->bd) hipFree(c->bd);
-    if (c->bh) hipHostFree(c->bh);
-    if (c->seqs) hipFree(c->seqs);
-    if (c->pool) hipFree(c->pool);
-    if (c->fpool) hipFree(c->fpool);
-    if (c->pin) hipHostFree(c->pin);
-    if (c->sth) hipHostFree(c->sth);
-    if (c->std_) hipFree(c->std_);
-    if (c->d_tables) hipFree(c->d_tables);
-    if (c->gz_pool) hipFree(c->gz_pool);
-    if (c->gzs_pool) hipFree(c->gzs_pool);
-    for (auto* g : {&c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h, &c->hc_small})
-        if (g->p) (void)(g->pinned ? hipHostFree(g->p) : hipFree(g->p));
-    if (c->ws_ev) { (void)hipEventSynchronize(c->ws_ev); (void)hipEventDestroy(c->ws_ev); }
-    if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    if (c->join_ev) (void)hipEventDestroy(c->join_ev);
-    if (c->side2) { (void)hipStreamSynchronize(c->side2); (void)hipStreamDestroy(c->side2); }
-    if (c->join2_ev) (void)hipEventDestroy(c->join2_ev);
-    if (c->mfork_ev) (void)hipEventDestroy(c->mfork_ev);
-    if (c->mjoin_ev) (void)hipEventDestroy(c->mjoin_ev);
-    for (auto& set : c->ev_sets)
-        for (auto& e : set) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    for (Side* sd : {&c->side, &c->side2}) {
+        if (sd->stream) { (void)hipStreamSynchronize(sd->stream); (void)hipStreamDestroy(sd->stream); }
+        if (sd->fork_ev) (void)hipEventDestroy(sd->fork_ev);
+        if (sd->join_ev) (void)hipEventDestroy(sd->join_ev);
+    }
     if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
+    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->seqs, &c->pool, &c->fpool,
+                   &c->sth, &c->std_, &c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h,
+                   &c->hc_small, &c->gz_pool, &c->gzs_pool})
+        b->release();
     for (auto& h : c->hs) {
-        (void)hipFree(h.d_data); (void)hipFree(h.d_offs); (void)hipFree(h.d_batches); (void)hipFree(h.d_records);
-        (void)hipFree(h.d_decoded);
-        (void)hipFree(h.d_sums); (void)hipFree(h.d_tot);
-        (void)hipFree(h.d_ist); (void)hipFree(h.d_ro); (void)hipFree(h.d_rt); (void)hipFree(h.d_ps);
-        if (h.h_tot) (void)hipHostFree(h.h_tot);
+        for (Buf* b : {&h.d_data, &h.d_offs, &h.d_batches, &h.d_records, &h.d_decoded, &h.d_sums, &h.d_tot, &h.h_tot,
+                       &h.d_ist, &h.d_ro, &h.d_rt, &h.d_ps})
+            b->release();
         if (h.h2d) hipEventDestroy(h.h2d);
         if (h.done) hipEventDestroy(h.done);
     }
+    if (c->d_tables) hipFree(c->d_tables);
+    for (hipEvent_t e : c->cev)
+        if (e) hipEventDestroy(e);
+    if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
+    for (auto& set : c->ev_sets)
+        for (auto& e : set) hipEventDestroy(e);
+    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return RPGPU_OK;
 }
@@ -490,48 +594,16 @@ int submit_impl(rpgpu_ctx* c, const rpgpu_job* job, void* stream, int stop, Plan
     if (!c) return RPGPU_E_INVALID;
     hipSetDevice(c->device);
     hipStream_t s = pick(c, stream);
-    if (int rc = ws_acquire(c, s)) return rc;
-    const int rc = submit_body(c, job, s, stop, plan);
-    const int rr = ws_release(c, s);
-    return rc ? rc : rr;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    if (int rc = submit_body(c, job, s, stop, plan)) return rc;
+    return scratch.release();
 }
 
-// grow-only device pool (drained before it is replaced)
-int grow_pool(rpgpu_ctx* c, void*& p, size_t& have, size_t want, hipStream_t s) {
-    if (want <= have && p) return RPGPU_OK;
-    if (p) {
-        if (int rc = ws_drain(c, s)) return rc;
-        (void)hipFree(p);
-        p = nullptr;
-        have = 0;
-    }
-    if (hipMalloc(&p, want) != hipSuccess) {
-        // not an error: without the pool every member is decoded by the
-        // second pass, straight into its arena slot
-        (void)hipGetLastError();
-        p = nullptr;
-        return RPGPU_OK;
-    }
-    have = want;
-    return RPGPU_OK;
-}
-
-// grow-only device or pinned host buffer (the stream is drained before a
-// device buffer is replaced: earlier work on the context may still use it)
-int grow_buf(rpgpu_ctx* c, rpgpu_ctx::Grow& g, size_t want, bool pinned, hipStream_t s) {
-    if (want <= g.bytes && g.p) return RPGPU_OK;
-    if (g.p) {
-        if (int rc = ws_drain(c, s)) return rc;
-        (void)(g.pinned ? hipHostFree(g.p) : hipFree(g.p));
-        g.p = nullptr;
-        g.bytes = 0;
-    }
-    want = std::max<size_t>(align_up(want + want / 4, 4096), 4096);
-    const hipError_t e = pinned ? hipHostMalloc(&g.p, want, hipHostMallocDefault) : hipMalloc(&g.p, want);
-    if (e != hipSuccess) { g.p = nullptr; return fail(c, RPGPU_E_NOMEM, "host codec staging"); }
-    g.bytes = want;
-    g.pinned = pinned;
-    return RPGPU_OK;
+// host-codec staging: 25 % slack over the job's bytes, whole pages
+int grow_staging(rpgpu_ctx* c, Buf& b, size_t want, hipStream_t s) {
+    if (want <= b.bytes) return RPGPU_OK;
+    return grow(c, b, std::max<size_t>(align_up(want + want / 4, 4096), 4096), s, "host codec staging");
 }
 
 // RPGPU_JOB_HOST_CODECS: the batches k_emit put on the host list (zstd) cross
@@ -542,15 +614,15 @@ int grow_buf(rpgpu_ctx* c, rpgpu_ctx::Grow& g, size_t want, bool pinned, hipStre
 // to 16, 0 when the reference throws), the bytes wait in device staging for
 // k_host_scatter.  Synchronizes the stream three times.
 int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
-    if (int rc = grow_buf(c, c->hc_small, 64, true, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_small, 64, s)) return rc;
     uint32_t* cnt = (uint32_t*)c->hc_small.p;
     HIPCHK(c, hipMemcpyAsync(cnt, j.counters + 19, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const uint32_t n = *cnt;
     if (n == 0) return RPGPU_OK;
     const size_t ib = (size_t)n * sizeof(HostItem);
-    if (int rc = grow_buf(c, c->hc_items, ib, false, s)) return rc;
-    if (int rc = grow_buf(c, c->hc_items_h, ib, true, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_items, ib, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_items_h, ib, s)) return rc;
     HostItem* dit = (HostItem*)c->hc_items.p;
     HostItem* hit = (HostItem*)c->hc_items_h.p;
     HIPCHK(c, launch_host_desc(j, dit, n, s));
@@ -561,8 +633,8 @@ int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
         hit[i].stage = in_total;
         in_total += align_up(hit[i].n, 16);
     }
-    if (int rc = grow_buf(c, c->hc_in, in_total + 16, false, s)) return rc;
-    if (int rc = grow_buf(c, c->hc_in_h, in_total + 16, true, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_in, in_total + 16, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_in_h, in_total + 16, s)) return rc;
     HIPCHK(c, hipMemcpyAsync(dit, hit, ib, hipMemcpyHostToDevice, s));
     HIPCHK(c, launch_host_gather(j, dit, n, (uint8_t*)c->hc_in.p, s));
     HIPCHK(c, hipMemcpyAsync(c->hc_in_h.p, c->hc_in.p, in_total, hipMemcpyDeviceToHost, s));
@@ -573,9 +645,7 @@ int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
     const uint8_t* in = (const uint8_t*)c->hc_in_h.p;
     std::atomic<uint32_t> next{0};
     std::atomic<bool> missing{false};
-    // RPGPU_HOST_CODEC_MISSING=1 (diagnostic build): act as if libzstd could
-    // not be loaded (tests the unsupported path)
-    static const bool force_missing = [] { const char* e = diag_env("RPGPU_HOST_CODEC_MISSING"); return e && *e == '1'; }();
+    const bool force_missing = diag().host_codec_missing;  // diagnostic build: tests the unsupported path
     auto work = [&]() {
         for (uint32_t i; (i = next.fetch_add(1)) < n;) {
             HostItem& it = hit[i];
@@ -613,8 +683,8 @@ int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
         it.stage = out_total;
         out_total += it.cap;
     }
-    if (int rc = grow_buf(c, c->hc_out, out_total + 16, false, s)) return rc;
-    if (int rc = grow_buf(c, c->hc_out_h, out_total + 16, true, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_out, out_total + 16, s)) return rc;
+    if (int rc = grow_staging(c, c->hc_out_h, out_total + 16, s)) return rc;
     for (uint32_t i = 0; i < n; i++)
         if (hit[i].status == 0) memcpy((uint8_t*)c->hc_out_h.p + hit[i].stage, outs[i].data(), hit[i].out_len);
     HIPCHK(c, hipMemcpyAsync(c->hc_out.p, c->hc_out_h.p, out_total, hipMemcpyHostToDevice, s));
@@ -626,7 +696,7 @@ int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
     return RPGPU_OK;
 }
 
-int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, PlanPtrs* plan) {
+int check_job(rpgpu_ctx* c, const rpgpu_job* job) {
     if (!c || !job || !job->d_data || !job->d_seg_offsets || !job->h_seg_offsets || job->n_segments == 0 ||
         !job->d_batches || !job->d_summaries || !job->d_totals)
         return fail(c, RPGPU_E_INVALID, "rpgpu_submit: missing argument");
@@ -635,8 +705,25 @@ int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, Pla
         return fail(c, RPGPU_E_INVALID, "rpgpu_submit: unknown layout");
     if ((job->flags & RPGPU_JOB_PARSE) && !job->d_records && job->record_capacity)
         return fail(c, RPGPU_E_INVALID, "rpgpu_submit: PARSE needs d_records");
+    return RPGPU_OK;
+}
+
+// Where each table of a job lies in the workspace (byte offsets, 256-byte
+// aligned), the capacities they were sized for and the bytes needed in all.
+struct Layout {
+    uint64_t tc;  // chunks of the job (every segment at least one)
+    uint64_t zcap, gcap, bl_cap, split_min, split_cap;
+    size_t cbase, chunks, ccount, centry, segterm, slots, dcap, counters, dlist, slist, llist, fbad;
+    size_t ilist, istate, ioff, itot, hlist, zitems, gzsmem, gzsit;
+    size_t blocks, plans, pstate, longl, wlong, rawl, lanel, lzfl, lzft, split, spart, scan;
+    size_t need;
+};
+
+Layout job_layout(const rpgpu_job* job, uint32_t cu_count) {
+    Layout L;
     const uint32_t nseg = job->n_segments;
     const uint32_t cs = job->chunk_bytes ? job->chunk_bytes : (256u << 10);
+    const uint64_t bcap = job->batch_capacity, data_len = job->h_seg_offsets[nseg];
     // chunk table from the host offsets
     uint64_t tc = 0;
     for (uint32_t i = 0; i < nseg; i++) {
@@ -644,67 +731,71 @@ int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, Pla
         uint64_t nc = (len + cs - 1) / cs;
         tc += nc ? nc : 1;
     }
-    if (tc > 0xFFFFFFF0ull) return fail(c, RPGPU_E_INVALID, "rpgpu_submit: too many chunks");
-    const uint64_t bcap = job->batch_capacity;
-    // workspace layout
+    L.tc = tc;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_cbase = take((nseg + 1) * 8);
-    const size_t o_chunks = take(tc * sizeof(ChunkRec));
-    const size_t o_ccount = take((tc + 1) * 8);
-    const size_t o_centry = take(tc * 8);
-    const size_t o_segterm = take(nseg * sizeof(SegTerm));
-    const size_t o_slots = take((bcap + 1) * 8);
-    const size_t o_dcap = take((bcap + 1) * 8);
-    const size_t o_counters = take(kCounterBytes);
-    const size_t o_dlist = take((bcap + 1) * 4);
-    const size_t o_slist = take((bcap + 1) * 4);
-    const size_t o_llist = take((bcap + 1) * 4);
-    const size_t o_fbad = take((size_t)nseg * 4);
+    L.cbase = take((nseg + 1) * 8);
+    L.chunks = take(tc * sizeof(ChunkRec));
+    L.ccount = take((tc + 1) * 8);
+    L.centry = take(tc * 8);
+    L.segterm = take(nseg * sizeof(SegTerm));
+    L.slots = take((bcap + 1) * 8);
+    L.dcap = take((bcap + 1) * 8);
+    L.counters = take(kCounterBytes);
+    L.dlist = take((bcap + 1) * 4);
+    L.slist = take((bcap + 1) * 4);
+    L.llist = take((bcap + 1) * 4);
+    L.fbad = take((size_t)nseg * 4);
     const bool decode_job = (job->flags & RPGPU_JOB_DECODE) != 0;
-    const size_t o_ilist = take(decode_job ? (bcap + 1) * 4 : 0);
-    const size_t o_istate = take(decode_job ? (bcap + 1) * 4 : 0);
-    const size_t o_ioff = take(decode_job ? (bcap + 1) * 8 : 0);
-    const size_t o_itot = take(decode_job ? (bcap + 1) * 8 : 0);
+    L.ilist = take(decode_job ? (bcap + 1) * 4 : 0);
+    L.istate = take(decode_job ? (bcap + 1) * 4 : 0);
+    L.ioff = take(decode_job ? (bcap + 1) * 8 : 0);
+    L.itot = take(decode_job ? (bcap + 1) * 8 : 0);
     const bool host_job = decode_job && (job->flags & RPGPU_JOB_HOST_CODECS);
-    const size_t o_hlist = take(host_job ? (bcap + 1) * 4 : 0);
+    L.hlist = take(host_job ? (bcap + 1) * 4 : 0);
     // zstd literal blocks planned ahead (k_zplan -> k_zlits): a 128 KiB block
     // each at most, so the job's bytes / 16 KiB + 8 per batch is ample (past
     // it, blocks decode in place)
-    const uint64_t zcap64 = decode_job ? std::min<uint64_t>(job->h_seg_offsets[nseg] / 16384 + 8 * bcap + 64, 0x7FFFFFFFull) : 0;
-    const size_t o_zitems = take(zcap64 * 8);
+    L.zcap = decode_job ? std::min<uint64_t>(data_len / 16384 + 8 * bcap + 64, 0x7FFFFFFFull) : 0;
+    L.zitems = take(L.zcap * 8);
     // gzip split decode: per member its first item and chunk count; items:
     // one per kGzsChunk deflate bytes of the split members, one more each
-    const size_t o_gzsmem = take(decode_job ? 2 * (bcap + 1) * 4 : 0);
-    const uint64_t gcap64 = decode_job ? std::min<uint64_t>(job->h_seg_offsets[nseg] / kGzsChunk + bcap + 64, 0x7FFFFFFFull) : 0;
-    const size_t o_gzsit = take(gcap64 * sizeof(GzsItem));
+    L.gzsmem = take(decode_job ? 2 * (bcap + 1) * 4 : 0);
+    L.gcap = decode_job ? std::min<uint64_t>(data_len / kGzsChunk + bcap + 64, 0x7FFFFFFFull) : 0;
+    L.gzsit = take(L.gcap * sizeof(GzsItem));
     // block-parallel decode: one item per LZ4F block / snappy-java chunk
-    const bool dec = (job->flags & RPGPU_JOB_DECODE) && job->d_decoded;
+    const bool dec = decode_job && job->d_decoded;
+    L.bl_cap = dec ? std::min<uint64_t>(data_len / 16384 + 2 * bcap + 64, 0x7FFFFFFFull) : 0;
+    L.blocks = take(L.bl_cap * sizeof(BlockItem));
+    L.plans = take(dec ? (bcap + 1) * sizeof(FramePlan) : 0);
+    L.pstate = take(L.bl_cap * sizeof(PieceState));
+    L.longl = take(L.bl_cap * 4);
+    L.wlong = take(L.bl_cap * 4);
+    L.rawl = take(L.bl_cap * 4);
+    L.lanel = take(L.bl_cap * 4);
+    L.lzfl = take(L.bl_cap * 4);
+    L.lzft = take(L.bl_cap * 4);
+    // the diagnostic override: scripts/bench_skew.py A/B
+    L.split_min = diag().split_min ? diag().split_min
+                                   : std::max<uint64_t>(kSplitMin, 2 * data_len / ((uint64_t)cu_count * kVWaves));
+    L.split_cap = std::min<uint64_t>(data_len / L.split_min + 1, bcap + 1);
+    L.split = take(L.split_cap * 4);
+    L.spart = take(L.split_cap * kSplitParts * 4);
+    L.scan = take(scan_temp_bytes(std::max<uint64_t>(tc, bcap)) + 64);
+    L.need = off;
+    return L;
+}
+
+// Grows the context's workspace and pools to the job's size and points the
+// DeviceJob at them.  The pools a job can do without (grow_optional) leave
+// their pointers null when they cannot be had.
+int bind_job(rpgpu_ctx* c, const rpgpu_job* job, const Layout& L, hipStream_t s, int stop, DeviceJob& j) {
+    const uint32_t nseg = job->n_segments;
     const uint64_t data_len = job->h_seg_offsets[nseg];
-    const uint64_t bl_cap64 = dec ? std::min<uint64_t>(data_len / 16384 + 2 * bcap + 64, 0x7FFFFFFFull) : 0;
-    const size_t o_blocks = take(bl_cap64 * sizeof(BlockItem));
-    const size_t o_plans = take(dec ? (bcap + 1) * sizeof(FramePlan) : 0);
-    const size_t o_pstate = take(bl_cap64 * sizeof(PieceState));
-    const size_t o_longl = take(bl_cap64 * 4);
-    const size_t o_wlong = take(bl_cap64 * 4);
-    const size_t o_rawl = take(bl_cap64 * 4);
-    const size_t o_lanel = take(bl_cap64 * 4);
-    const size_t o_lzfl = take(bl_cap64 * 4);
-    const size_t o_lzft = take(bl_cap64 * 4);
-    uint64_t split_min = std::max<uint64_t>(kSplitMin, 2 * data_len / ((uint64_t)c->cu_count * kVWaves));
-    // RPGPU_SPLIT_MIN_KIB (diagnostic build): override (scripts/bench_skew.py A/B)
-    if (const char* e = diag_env("RPGPU_SPLIT_MIN_KIB")) split_min = std::max<uint64_t>(strtoull(e, nullptr, 10) << 10, 64);
-    const uint64_t split_cap = std::min<uint64_t>(data_len / split_min + 1, bcap + 1);
-    const size_t o_split = take(split_cap * 4);
-    const size_t o_spart = take(split_cap * kSplitParts * 4);
-    const size_t o_scan = take(scan_temp_bytes(std::max<uint64_t>(tc, bcap)) + 64);
-    const size_t need = off;
-    if (dec && !c->seqs) {
+    const bool dec = (job->flags & RPGPU_JOB_DECODE) && job->d_decoded;
+    if (dec && !c->seqs.p) {
         const uint32_t waves = c->cu_count * lz_exec_wgs_per_cu();
-        if (hipMalloc(&c->seqs, (size_t)waves * kRecsPerLane * sizeof(SeqRec)) != hipSuccess) {
-            c->seqs = nullptr;
-            return fail(c, RPGPU_E_NOMEM, "decode sequence workspace");
-        }
+        if (int rc = grow(c, c->seqs, (size_t)waves * kRecsPerLane * sizeof(SeqRec), s, "decode sequence workspace")) return rc;
         c->exec_waves = waves;
     }
     // record pool: a compressed LZ4 byte yields at most 1/3 record (16 B),
@@ -713,45 +804,27 @@ int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, Pla
     // k_lz_exec itself
     const size_t slab_bytes = kSlabRecs * sizeof(SeqRec) + 4;
     const size_t pool_want = dec ? std::min<size_t>(std::max<size_t>(data_len / 2, 256ull << 20), 8ull << 30) : 0;
-    if (pool_want > c->pool_bytes) {
-        if (c->pool) {
-            if (int rc = ws_drain(c, s)) return rc;
-            hipFree(c->pool);
-            c->pool = nullptr;
-            c->pool_bytes = 0;
-        }
-        if (hipMalloc(&c->pool, pool_want) != hipSuccess) { c->pool = nullptr; return fail(c, RPGPU_E_NOMEM, "decode record pool"); }
-        c->pool_bytes = pool_want;
-    }
-    if (need > c->ws_bytes) {
-        if (c->ws) {
-            if (int rc = ws_drain(c, s)) return rc;
-            hipFree(c->ws);
-            c->ws = nullptr;
-        }
-        if (hipMalloc(&c->ws, need) != hipSuccess) { c->ws_bytes = 0; return fail(c, RPGPU_E_NOMEM, "workspace"); }
-        c->ws_bytes = need;
-    }
-    uint8_t* ws = (uint8_t*)c->ws;
+    if (int rc = grow(c, c->pool, pool_want, s, "decode record pool")) return rc;
+    if (int rc = grow(c, c->ws, L.need, s, "workspace")) return rc;
+    uint8_t* ws = c->ws.as<uint8_t>();
 
-    DeviceJob j;
     j.data = job->d_data;
-    j.data_len = job->h_seg_offsets[nseg];
+    j.data_len = data_len;
     j.seg_off = job->d_seg_offsets;
-    j.chunk_base = (const uint64_t*)(ws + o_cbase);
+    j.chunk_base = (const uint64_t*)(ws + L.cbase);
     j.n_segments = nseg;
     j.flags = job->flags;
     j.layout = job->layout;
-    j.chunk_bytes = cs;
-    j.total_chunks = (uint32_t)tc;
-    j.chunks = (ChunkRec*)(ws + o_chunks);
-    j.chunk_count = (uint64_t*)(ws + o_ccount);
-    j.chunk_entry = (uint64_t*)(ws + o_centry);
-    j.seg_term = (SegTerm*)(ws + o_segterm);
+    j.chunk_bytes = job->chunk_bytes ? job->chunk_bytes : (256u << 10);
+    j.total_chunks = (uint32_t)L.tc;
+    j.chunks = (ChunkRec*)(ws + L.chunks);
+    j.chunk_count = (uint64_t*)(ws + L.ccount);
+    j.chunk_entry = (uint64_t*)(ws + L.centry);
+    j.seg_term = (SegTerm*)(ws + L.segterm);
     j.batches = job->d_batches;
-    j.batch_capacity = bcap;
-    j.slots = (uint64_t*)(ws + o_slots);
-    j.dcap = (uint64_t*)(ws + o_dcap);
+    j.batch_capacity = job->batch_capacity;
+    j.slots = (uint64_t*)(ws + L.slots);
+    j.dcap = (uint64_t*)(ws + L.dcap);
     j.records = job->d_records;
     j.record_capacity = job->d_records ? job->record_capacity : 0;
     j.decoded = job->d_decoded;
@@ -760,192 +833,155 @@ int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, Pla
     j.totals = job->d_totals;
     j.bitmap = job->d_valid_bitmap;
     j.tables = c->d_tables;
-    j.counters = (uint32_t*)(ws + o_counters);
-    j.decode_list = (uint32_t*)(ws + o_dlist);
-    j.seq_list = (uint32_t*)(ws + o_slist);
-    j.link_list = (uint32_t*)(ws + o_llist);
-    j.long_list = (uint32_t*)(ws + o_longl);
-    j.wlong_list = (uint32_t*)(ws + o_wlong);
-    j.raw_list = (dec && stop == kRunAll) ? (uint32_t*)(ws + o_rawl) : nullptr;
-    j.lane_list = (uint32_t*)(ws + o_lanel);
-    j.split_list = (uint32_t*)(ws + o_split);
-    j.split_part = (uint32_t*)(ws + o_spart);
-    j.split_capacity = (uint32_t)split_cap;
-    j.split_min = split_min;
-    j.seqs = c->seqs;
+    j.counters = (uint32_t*)(ws + L.counters);
+    j.decode_list = (uint32_t*)(ws + L.dlist);
+    j.seq_list = (uint32_t*)(ws + L.slist);
+    j.link_list = (uint32_t*)(ws + L.llist);
+    j.long_list = (uint32_t*)(ws + L.longl);
+    j.wlong_list = (uint32_t*)(ws + L.wlong);
+    j.raw_list = (dec && stop == kRunAll) ? (uint32_t*)(ws + L.rawl) : nullptr;
+    j.lane_list = (uint32_t*)(ws + L.lanel);
+    j.split_list = (uint32_t*)(ws + L.split);
+    j.split_part = (uint32_t*)(ws + L.spart);
+    j.split_capacity = (uint32_t)L.split_cap;
+    j.split_min = L.split_min;
+    j.seqs = c->seqs.as<SeqRec>();
     j.exec_waves = c->exec_waves;
-    j.pstate = (PieceState*)(ws + o_pstate);
-    j.pool_slabs = (uint32_t)std::min<size_t>(c->pool_bytes / slab_bytes, 0xFFFFFFF0ull);
-    // RPGPU_POOL_SLABS (diagnostic build): shrinks the record pool (exercises
-    // k_lz_exec's own walk of the pieces the pool cuts short)
-    if (const char* e = diag_env("RPGPU_POOL_SLABS")) j.pool_slabs = std::min<uint32_t>(j.pool_slabs, (uint32_t)atoi(e));
-    j.pool = (SeqRec*)c->pool;
+    j.pstate = (PieceState*)(ws + L.pstate);
+    // the diagnostic cap shrinks the record pool (exercises k_lz_exec's own
+    // walk of the pieces the pool cuts short)
+    j.pool_slabs = std::min((uint32_t)std::min<size_t>(c->pool.bytes / slab_bytes, 0xFFFFFFF0ull), diag().pool_slabs);
+    j.pool = c->pool.as<SeqRec>();
+    j.crc_compose = diag().crc_compose ? 1u : 0u;
     // the decoded payloads' record chains (k_dchain) reuse the record pool,
-    // idle once decode is done: one u32 per index slot.  RPGPU_DCHAIN=0
-    // (diagnostic build): k_validate_decoded chains the records itself (A/B)
-    // RPGPU_CRC_COMPOSE=0 (diagnostic build): k_validate streams every stored payload (A/B)
-    static const bool compose_on = [] { const char* e = diag_env("RPGPU_CRC_COMPOSE"); return !(e && *e == '0'); }();
-    j.crc_compose = compose_on ? 1u : 0u;
-    static const bool dchain_on = [] { const char* e = diag_env("RPGPU_DCHAIN"); return !(e && *e == '0'); }();
-    j.dchain = (dec && dchain_on && c->pool && (uint64_t)c->pool_bytes / 4 >= j.record_capacity) ? (uint32_t*)c->pool
-                                                                                                  : nullptr;
-    j.slab_next = (uint32_t*)((uint8_t*)c->pool + (size_t)j.pool_slabs * kSlabRecs * sizeof(SeqRec));
+    // idle once decode is done: one u32 per index slot
+    j.dchain = (dec && diag().dchain && c->pool.p && (uint64_t)c->pool.bytes / 4 >= j.record_capacity) ? c->pool.as<uint32_t>()
+                                                                                                      : nullptr;
+    j.slab_next = (uint32_t*)(c->pool.as<uint8_t>() + (size_t)j.pool_slabs * kSlabRecs * sizeof(SeqRec));
     // fast-path records: the planner reserves csize / 3 + 2 per listed LZ4
     // block (2.7 bytes per compressed byte; C2 uses 0.3 of the job's bytes),
     // 3x the job's bytes (a job of nothing but LZ4 blocks fits whole), 64 MiB
     // .. 16 GiB; a group of blocks that finds no room (and every group after
-    // it) takes the walk / exec kernels, with the same results.
-    // RPGPU_LZF=0 (diagnostic build): every piece through the walk / exec (A/B);
-    // RPGPU_FREC_CAP=n (diagnostic build): at most n records (mixes listed
-    // groups with walked ones in small jobs; tests/test_gpu_diag.py)
+    // it) takes the walk / exec kernels, with the same results.  The
+    // diagnostic record cap mixes listed groups with walked ones in small
+    // jobs (tests/test_gpu_diag.py)
     j.frecs = nullptr;
     j.frec_cap = 0;
     j.lzf_list = nullptr;
     j.lzf_tail = nullptr;
-    static const bool lzf_on = [] { const char* e = diag_env("RPGPU_LZF"); return !(e && *e == '0'); }();
-    if (dec && lzf_on && stop == kRunAll) {
+    if (dec && diag().lzf && stop == kRunAll) {
         const size_t want = std::min<size_t>(std::max<size_t>(data_len * 3, 64ull << 20), 16ull << 30);
-        if (int rc = grow_pool(c, c->fpool, c->fpool_bytes, want, s)) return rc;
-        if (c->fpool) {
-            j.frecs = (uint2*)c->fpool;
-            j.frec_cap = c->fpool_bytes / sizeof(uint2);
-            if (const char* e = diag_env("RPGPU_FREC_CAP")) j.frec_cap = std::min<uint64_t>(j.frec_cap, strtoull(e, nullptr, 10));
-            j.lzf_list = (uint32_t*)(ws + o_lzfl);
-            j.lzf_tail = (uint32_t*)(ws + o_lzft);
+        if (int rc = grow_optional(c, c->fpool, want, s)) return rc;
+        if (c->fpool.p) {
+            j.frecs = c->fpool.as<uint2>();
+            j.frec_cap = std::min<uint64_t>(c->fpool.bytes / sizeof(uint2), diag().frec_cap);
+            j.lzf_list = (uint32_t*)(ws + L.lzfl);
+            j.lzf_tail = (uint32_t*)(ws + L.lzft);
         }
     }
-    j.seg_first_bad = (uint32_t*)(ws + o_fbad);
+    j.seg_first_bad = (uint32_t*)(ws + L.fbad);
     j.seeds = (job->d_seeds && job->d_seed_offsets) ? job->d_seeds : nullptr;
     j.seed_off = j.seeds ? job->d_seed_offsets : nullptr;
-    j.inf_list = (uint32_t*)(ws + o_ilist);
-    j.inf_state = (uint32_t*)(ws + o_istate);
-    j.inf_off = (uint64_t*)(ws + o_ioff);
-    j.inf_total = (uint64_t*)(ws + o_itot);
+    j.inf_list = (uint32_t*)(ws + L.ilist);
+    j.inf_state = (uint32_t*)(ws + L.istate);
+    j.inf_off = (uint64_t*)(ws + L.ioff);
+    j.inf_total = (uint64_t*)(ws + L.itot);
     // gzip first-pass pool: twice the job's bytes, 256 MiB .. 2 GiB (members
-    // that do not fit are decoded again, straight into the arena)
+    // that do not fit are decoded again, straight into the arena); the
+    // diagnostic size exercises members that do not get a scratch slot.
+    // Only a job that writes decoded bytes uses it (a planning run only sizes
+    // members); failing to get it costs a second pass, never the job.
     j.inf_scratch = nullptr;
     j.inf_scratch_bytes = 0;
     j.inf_scratch_used = (uint64_t*)(j.counters + 24);  // zeroed with the counters
-    // Only a job that writes decoded bytes uses it (a planning run only sizes
-    // members); failing to get it costs a second pass, never the job.
     if (dec && stop == kRunAll) {
-        size_t want = std::min<size_t>(std::max<size_t>(2 * data_len, 256ull << 20), 2ull << 30);
-        // RPGPU_INF_POOL_KIB (diagnostic build): a small pool (exercises members
-        // that do not get a scratch slot)
-        if (const char* e = diag_env("RPGPU_INF_POOL_KIB")) want = std::max<size_t>(strtoull(e, nullptr, 10) << 10, 4096);
-        if (int rc = grow_pool(c, c->gz_pool, c->gz_pool_bytes, want, s)) return rc;
-        if (c->gz_pool) {
-            j.inf_scratch = (uint8_t*)c->gz_pool;
-            j.inf_scratch_bytes = std::min<size_t>(c->gz_pool_bytes, want);
+        const size_t want = diag().inf_pool ? diag().inf_pool
+                                            : std::min<size_t>(std::max<size_t>(2 * data_len, 256ull << 20), 2ull << 30);
+        if (int rc = grow_optional(c, c->gz_pool, want, s)) return rc;
+        if (c->gz_pool.p) {
+            j.inf_scratch = c->gz_pool.as<uint8_t>();
+            j.inf_scratch_bytes = std::min<size_t>(c->gz_pool.bytes, want);
         }
     }
-    // RPGPU_ZS_FAST=0 (diagnostic build): every zstd member through the wave decoder (A/B)
-    static const uint32_t zs_fast = [] { const char* e = diag_env("RPGPU_ZS_FAST"); return e && *e == '0' ? 0u : 1u; }();
-    j.zs_fast = zs_fast;
+    j.zs_fast = diag().zs_fast;
     j.zs_split = 0;
-    j.zs_items = (uint64_t*)(ws + o_zitems);
-    j.zs_items_cap = (uint32_t)zcap64;
-    j.host_list = (uint32_t*)(ws + o_hlist);
+    j.zs_items = (uint64_t*)(ws + L.zitems);
+    j.zs_items_cap = (uint32_t)L.zcap;
+    j.host_list = (uint32_t*)(ws + L.hlist);
     // the gzip split decode (with the scratch pool only: it writes the
-    // members' bytes there); RPGPU_GZS=0 (diagnostic build): every gzip member
-    // serial (A/B)
+    // members' bytes there)
     j.gzs_mem = nullptr;
-    j.gzs_items = (GzsItem*)(ws + o_gzsit);
-    j.gzs_items_cap = (uint32_t)gcap64;
+    j.gzs_items = (GzsItem*)(ws + L.gzsit);
+    j.gzs_items_cap = (uint32_t)L.gcap;
     j.gzs_pool = nullptr;
     j.gzs_pool_syms = 0;
-#ifdef RPGPU_NO_GZS  // A/B variant (scripts/build_exp.py): every gzip member serial
-    static const bool gzs_on = false;
-#else
-    static const bool gzs_on = [] { const char* e = diag_env("RPGPU_GZS"); return !(e && *e == '0'); }();
-#endif
-    if (j.inf_scratch && gzs_on && gcap64) {
+    if (j.inf_scratch && diag().gzs && L.gcap) {
         const size_t want = std::min<size_t>(std::max<size_t>(2 * data_len, 64ull << 20), 4ull << 30);
-        if (int rc = grow_pool(c, c->gzs_pool, c->gzs_pool_bytes, want, s)) return rc;
-        if (c->gzs_pool) {
-            j.gzs_mem = (uint32_t*)(ws + o_gzsmem);
-            j.gzs_pool = (uint16_t*)c->gzs_pool;
-            j.gzs_pool_syms = c->gzs_pool_bytes / 2;
+        if (int rc = grow_optional(c, c->gzs_pool, want, s)) return rc;
+        if (c->gzs_pool.p) {
+            j.gzs_mem = (uint32_t*)(ws + L.gzsmem);
+            j.gzs_pool = c->gzs_pool.as<uint16_t>();
+            j.gzs_pool_syms = c->gzs_pool.bytes / 2;
         }
     }
     c->hc_n = 0;
-    j.blocks = (BlockItem*)(ws + o_blocks);
-    j.block_capacity = (uint32_t)bl_cap64;
-    j.plans = (FramePlan*)(ws + o_plans);
+    j.blocks = (BlockItem*)(ws + L.blocks);
+    j.block_capacity = (uint32_t)L.bl_cap;
+    j.plans = (FramePlan*)(ws + L.plans);
     if (((uintptr_t)job->d_decoded & 15) != 0) return fail(c, RPGPU_E_INVALID, "rpgpu_submit: d_decoded must be 16-byte aligned");
-    uint64_t* scan_tmp = (uint64_t*)(ws + o_scan);
+    return RPGPU_OK;
+}
 
-    // RPGPU_DEBUG_SYNC=1 (diagnostic build): synchronize after every stage and
-    // name the stage that failed (fault localisation)
-    static const bool dbg = [] { const char* e = diag_env("RPGPU_DEBUG_SYNC"); return e && *e == '1'; }();
+// One launch (or scan) of the pipeline; with RPGPU_DEBUG_SYNC=1 (diagnostic
+// build) every stage is synchronized and the one that failed is named (fault
+// localisation).  Expects `c` and `s` in scope.
 #define STAGE(name, call)                                                                  \
     do {                                                                                   \
         HIPCHK(c, (call));                                                                 \
-        if (dbg) {                                                                         \
+        if (diag().debug_sync) {                                                           \
             fprintf(stderr, "[rpgpu] stage %s\n", name);                                   \
             fflush(stderr);                                                                \
             hipError_t _e = hipStreamSynchronize(s);                                       \
-            if (_e == hipSuccess && c->side) _e = hipStreamSynchronize(c->side);           \
-            if (_e == hipSuccess && c->side2) _e = hipStreamSynchronize(c->side2);         \
+            if (_e == hipSuccess && c->side.stream) _e = hipStreamSynchronize(c->side.stream);   \
+            if (_e == hipSuccess && c->side2.stream) _e = hipStreamSynchronize(c->side2.stream); \
             if (_e != hipSuccess) return fail(c, RPGPU_E_HIP, "stage " name " failed", _e); \
         }                                                                                  \
     } while (0)
-    // timed submits only: rpgpu_query_capacity's planning runs stop early
-    // and record no timings
-    const bool tm = c->timing && stop == kRunAll;
-    hipEvent_t* ev = nullptr;
-    if (tm) {
-        if (c->ev_used == c->ev_sets.size()) {
-            std::array<hipEvent_t, 7> set;
-            for (auto& e : set) HIPCHK(c, hipEventCreate(&e));
-            c->ev_sets.push_back(set);
-        }
-        ev = c->ev_sets[c->ev_used++].data();
-        HIPCHK(c, hipEventRecord(ev[0], s));
-    }
+
+// timing event i of a timed submit (ev = nullptr: not timed)
+hipError_t mark(hipEvent_t* ev, int i, hipStream_t s) { return ev ? hipEventRecord(ev[i], s) : hipSuccess; }
+
+// discover -> resolve -> the batch count per chunk, scanned; then (emit) the
+// batch results' slots.  A counting run (kStopAfterCount) stops before emit.
+int stage_discover(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s, hipEvent_t* ev, uint64_t* scan_tmp, bool emit) {
     STAGE("chunk_base", launch_chunk_base(j, s));
     HIPCHK(c, hipMemsetAsync(j.counters, 0, kCounterBytes, s));
-    HIPCHK(c, hipMemsetAsync(j.seg_first_bad, 0xFF, (size_t)nseg * 4, s));
+    HIPCHK(c, hipMemsetAsync(j.seg_first_bad, 0xFF, (size_t)j.n_segments * 4, s));
     STAGE("discover", launch_discover(j, s));
-    if (tm) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, mark(ev, 1, s));
     STAGE("resolve", launch_resolve(j, s));
-    STAGE("scan_chunks", scan_exclusive_u64(j.chunk_count, tc, scan_tmp, 0, s));
-    if (plan) {
-        plan->n_batches = j.chunk_count + tc;
-        plan->slots = j.slots;
-        plan->dcap = j.dcap;
-    }
-    if (stop == kStopAfterCount) return RPGPU_OK;
-    STAGE("emit", launch_emit(j, s));
-    // gzip members: the first pass (their arena bytes, index slots and, when
-    // they fit the pool, their output) before the scans
-    if (decode_job) {
+    STAGE("scan_chunks", scan_exclusive_u64(j.chunk_count, j.total_chunks, scan_tmp, 0, s));
+    if (emit) STAGE("emit", launch_emit(j, s));
+    return RPGPU_OK;
+}
+
+// gzip / zstd members: the first pass (their arena bytes, index slots and,
+// when they fit the pool, their output), the host-codec step, then the scans
+// of the index slots and the arena reservations
+int stage_members(rpgpu_ctx* c, DeviceJob& j, hipStream_t s, uint64_t* scan_tmp) {
+    const uint32_t cus = c->cu_count;
+    if (j.flags & RPGPU_JOB_DECODE) {
         // zstd members on the side stream when the lane parser can run (it
         // needs the scratch pool), gzip members (and, otherwise, zstd ones) here
         const bool split = j.inf_scratch && j.zs_fast;
         STAGE("zstamps", launch_zstamps(s, 0));
-        // an error return between the fork and the join still orders `s`
-        // after the side stream's kernels (the workspace is released on `s`)
-        struct SideJoin {
-            hipStream_t s = nullptr, side = nullptr;
-            hipEvent_t ev = nullptr;
-            ~SideJoin() {
-                if (side && hipEventRecord(ev, side) == hipSuccess) hipStreamWaitEvent(s, ev, 0);
-            }
-        } side_join;
+        Fork zfork;
         if (split) {
-            if (!c->side) HIPCHK(c, side_stream_create(&c->side));
-            if (!c->fork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-            if (!c->join_ev) HIPCHK(c, hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming));
             j.zs_split = 1;
-            HIPCHK(c, hipEventRecord(c->fork_ev, s));
-            HIPCHK(c, hipStreamWaitEvent(c->side, c->fork_ev, 0));
-            side_join.s = s;
-            side_join.ev = c->join_ev;
-            side_join.side = c->side;
-            STAGE("zplan", launch_zplan(j, c->side, c->cu_count * 4));
-            STAGE("zparse", launch_zparse(j, c->side, c->cu_count * 4));
-            HIPCHK(c, hipEventRecord(c->join_ev, c->side));
+            HIPCHK(c, zfork.open(s, c->side));
+            STAGE("zplan", launch_zplan(j, c->side.stream, cus * 4));
+            STAGE("zparse", launch_zparse(j, c->side.stream, cus * 4));
+            HIPCHK(c, zfork.end());
         }
         // the split decode's members first, then the serial first pass over
         // the rest and over the members the split decode did not close
@@ -955,200 +991,156 @@ int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, Pla
             // wave each) beside the split decode's k_gzsdecode, on the
             // raw-copy stream (idle until the decode stage), the rest after
             // it.  (Forked before k_gzsfind instead, they slowed it 14.3 ->
-            // 19.9 ms: C6 resolve+plan 58.9 against 56.7 ms.)  Diagnostic build:
-            // RPGPU_MEM_SIDE=0 all after the split decode, 1 forked before k_gzsfind
-            static const int mem_side = [] { const char* e = diag_env("RPGPU_MEM_SIDE"); return e ? atoi(e) : 2; }();
-            if (mem_side == 2) STAGE("gzsfind", launch_gzsplit(j, s, c->cu_count, 1));
-            struct MemJoin {
-                hipStream_t s = nullptr, side = nullptr;
-                hipEvent_t ev = nullptr;
-                ~MemJoin() {
-                    if (side && hipEventRecord(ev, side) == hipSuccess) hipStreamWaitEvent(s, ev, 0);
-                }
-            } mem_join;
-            if (mem_side) {
-                if (!c->side2) HIPCHK(c, side_stream_create(&c->side2));
-                if (!c->mfork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->mfork_ev, hipEventDisableTiming));
-                if (!c->mjoin_ev) HIPCHK(c, hipEventCreateWithFlags(&c->mjoin_ev, hipEventDisableTiming));
-                HIPCHK(c, hipEventRecord(c->mfork_ev, s));
-                HIPCHK(c, hipStreamWaitEvent(c->side2, c->mfork_ev, 0));
-                mem_join.s = s;
-                mem_join.ev = c->mjoin_ev;
-                mem_join.side = c->side2;
-                STAGE("inflate_plan", launch_inflate_plan(j, c->side2, c->cu_count * 4, 1));
-                HIPCHK(c, hipEventRecord(c->mjoin_ev, c->side2));
-            }
-            STAGE("gzsplit", launch_gzsplit(j, s, c->cu_count, mem_side == 2 ? 2 : 0));
-            STAGE("inflate_plan", launch_inflate_plan(j, s, c->cu_count * 4, mem_side ? 2 : 0));
-            if (mem_side) {
-                HIPCHK(c, hipStreamWaitEvent(s, c->mjoin_ev, 0));
-                mem_join.side = nullptr;  // joined
-            }
+            // 19.9 ms: C6 resolve+plan 58.9 against 56.7 ms.)
+            STAGE("gzsfind", launch_gzsplit(j, s, cus, 1));
+            Fork mfork;
+            HIPCHK(c, mfork.open(s, c->side2));
+            STAGE("inflate_plan", launch_inflate_plan(j, c->side2.stream, cus * 4, 1));
+            HIPCHK(c, mfork.end());
+            STAGE("gzsplit", launch_gzsplit(j, s, cus, 2));
+            STAGE("inflate_plan", launch_inflate_plan(j, s, cus * 4, 2));
+            HIPCHK(c, mfork.join());
         } else {
-            STAGE("inflate_plan", launch_inflate_plan(j, s, c->cu_count * 4));
+            STAGE("inflate_plan", launch_inflate_plan(j, s, cus * 4));
         }
         if (split) {
-            HIPCHK(c, hipStreamWaitEvent(s, c->join_ev, 0));
-            side_join.side = nullptr;  // joined
-            STAGE("zfallback", launch_zfallback(j, s, c->cu_count * 4));
+            HIPCHK(c, zfork.join());
+            STAGE("zfallback", launch_zfallback(j, s, cus * 4));
         }
         // zstd members whose corrupt stream reads ring bytes the current
         // segment has overwritten: decoded again over libzstd's exact buffer
         STAGE("zexact", launch_zexact(j, s, 0));
         STAGE("zstamps", launch_zstamps(s, 1));
+        // zstd members (RPGPU_JOB_HOST_CODECS): decoded on the host now, sized
+        // before the scans like every other payload
+        if (j.flags & RPGPU_JOB_HOST_CODECS)
+            if (int rc = host_codec_step(c, j, s)) return rc;
     }
-    // zstd members (RPGPU_JOB_HOST_CODECS): decoded on the host now, sized
-    // before the scans like every other payload
-    if (host_job)
-        if (int rc = host_codec_step(c, j, s)) return rc;
-    const uint64_t* d_nb = j.chunk_count + tc;
-    STAGE("scan_slots", scan_exclusive_u64_devn(j.slots, d_nb, bcap, scan_tmp, s));
+    const uint64_t* d_nb = j.chunk_count + j.total_chunks;
+    STAGE("scan_slots", scan_exclusive_u64_devn(j.slots, d_nb, j.batch_capacity, scan_tmp, s));
     // without DECODE every reservation is 0 (k_emit): the scan would write
     // zeros over zeros; k_finalize_totals reads no total then
-    if (job->flags & RPGPU_JOB_DECODE) STAGE("scan_dcap", scan_exclusive_u64_devn(j.dcap, d_nb, bcap, scan_tmp, s));
-    if (stop == kStopAfterPlan) return RPGPU_OK;
-    if (tm) HIPCHK(c, hipEventRecord(ev[2], s));
-    // k_content_xxh's side stream (below) joins s on every return, error paths too
-    struct SideJoin {
-        hipStream_t s = nullptr, side = nullptr;
-        hipEvent_t ev = nullptr;
-        ~SideJoin() {
-            if (side && hipEventRecord(ev, side) == hipSuccess) hipStreamWaitEvent(s, ev, 0);
+    if (j.flags & RPGPU_JOB_DECODE) STAGE("scan_dcap", scan_exclusive_u64_devn(j.dcap, d_nb, j.batch_capacity, scan_tmp, s));
+    return RPGPU_OK;
+}
+
+// decode, before validate: k_validate checksums and walks the decoded
+// payloads.  xside: the content checksums on the side stream.
+int stage_decode(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s, bool xside) {
+    const uint32_t cus = c->cu_count;
+    STAGE("decode", launch_decode(j, s, cus * 8));
+    STAGE("decode_blocks", launch_decode_blocks(j, s, cus * 8));
+    {
+        // the listed LZ4 blocks (k_lzf_walk + k_lzf_tail) on the side
+        // stream, every other piece (k_lz_walk) here: the planner fixed
+        // the two sets (BlockItem.fast), so they run side by side
+        const bool lzf = j.lzf_list != nullptr;
+        Fork lzf_fork, raw_fork;
+        if (lzf) {
+            HIPCHK(c, lzf_fork.open(s, c->side));
+            STAGE("lzf_walk", launch_lzf_walk(j, c->side.stream, cus));
+            HIPCHK(c, lzf_fork.end());
         }
-    } xjoin;
-    bool xside = false;
-    // decode first: k_validate checksums and walks the decoded payloads
-    if ((job->flags & RPGPU_JOB_DECODE) && j.decoded) {
-        STAGE("decode", launch_decode(j, s, c->cu_count * 8));
-        STAGE("decode_blocks", launch_decode_blocks(j, s, c->cu_count * 8));
-        {
-            // the listed LZ4 blocks (k_lzf_walk + k_lzf_tail) on the side
-            // stream, every other piece (k_lz_walk) here: the planner fixed
-            // the two sets (BlockItem.fast), so they run side by side
-            struct LzfJoin {
-                hipStream_t s = nullptr, side = nullptr;
-                hipEvent_t ev = nullptr;
-                ~LzfJoin() {
-                    if (side && hipEventRecord(ev, side) == hipSuccess) hipStreamWaitEvent(s, ev, 0);
-                }
-            } lzf_join, raw_join;
-            const bool lzf = j.lzf_list != nullptr;
-            // RPGPU_WALK_FIRST=1 (diagnostic build): k_lz_walk submitted before
-            // the side streams' kernels (dispatch-order A/B)
-            static const bool walk_first = [] { const char* e = diag_env("RPGPU_WALK_FIRST"); return e && *e == '1'; }();
-            bool walked = false;
-            // RPGPU_LZWALK_WGS (diagnostic build): k_lz_walk's grid (workgroups)
-            static const uint32_t lzw_env = [] { const char* e = diag_env("RPGPU_LZWALK_WGS"); return e ? (uint32_t)atoi(e) : 0u; }();
-            const uint32_t lzw_grid = lzw_env ? lzw_env : c->cu_count * 16;
-            if (lzf) {
-                if (!c->side) HIPCHK(c, side_stream_create(&c->side));
-                if (!c->fork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-                if (!c->join_ev) HIPCHK(c, hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming));
-                HIPCHK(c, hipEventRecord(c->fork_ev, s));
-                HIPCHK(c, hipStreamWaitEvent(c->side, c->fork_ev, 0));
-                if (walk_first) {
-                    STAGE("lz_walk", launch_lz_walk(j, s, lzw_grid));
-                    walked = true;
-                }
-                lzf_join.s = s;
-                lzf_join.ev = c->join_ev;
-                lzf_join.side = c->side;
-                STAGE("lzf_walk", launch_lzf_walk(j, c->side, c->cu_count));
-                HIPCHK(c, hipEventRecord(c->join_ev, c->side));
-            }
-            // the raw copies on a stream of their own, so that neither walk
-            // waits for them (C5: the longest raw snappy walk, ~3.7 ms, began
-            // after ~0.45 ms of copies).  RPGPU_RAW_SERIAL=1 (diagnostic
-            // build): after the join (A/B of the overlap); RPGPU_RAW_STREAM=0:
-            // before k_lz_walk on the job's stream (round-5 order)
-            static const bool raw_serial = [] { const char* e = diag_env("RPGPU_RAW_SERIAL"); return e && *e == '1'; }();
-            static const bool raw_own = [] { const char* e = diag_env("RPGPU_RAW_STREAM"); return !(e && *e == '0'); }();
-            if (!raw_serial && lzf && raw_own && j.raw_list) {
-                // RPGPU_RAW_PRIO=0 (diagnostic build): the raw-copy stream at the default priority (A/B)
-                static const bool raw_prio = [] { const char* e = diag_env("RPGPU_RAW_PRIO"); return !(e && *e == '0'); }();
-                if (!c->side2) HIPCHK(c, raw_prio ? side_stream_create(&c->side2) : hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
-                if (!c->join2_ev) HIPCHK(c, hipEventCreateWithFlags(&c->join2_ev, hipEventDisableTiming));
-                HIPCHK(c, hipStreamWaitEvent(c->side2, c->fork_ev, 0));
-                raw_join.s = s;
-                raw_join.ev = c->join2_ev;
-                raw_join.side = c->side2;
-                STAGE("raw_copy", launch_raw_copy(j, c->side2, c->cu_count));
-                HIPCHK(c, hipEventRecord(c->join2_ev, c->side2));
-            } else if (!raw_serial) {
-                STAGE("raw_copy", launch_raw_copy(j, s, c->cu_count));
-            }
-            if (!walked) STAGE("lz_walk", launch_lz_walk(j, s, lzw_grid));
-            if (lzf) {
-                HIPCHK(c, hipStreamWaitEvent(s, c->join_ev, 0));
-                lzf_join.side = nullptr;  // joined
-            }
-            if (raw_join.side) {
-                HIPCHK(c, hipStreamWaitEvent(s, c->join2_ev, 0));
-                raw_join.side = nullptr;
-            }
-            if (raw_serial) STAGE("raw_copy", launch_raw_copy(j, s, c->cu_count));
+        // the raw copies on a stream of their own, so that neither walk
+        // waits for them (C5: the longest raw snappy walk, ~3.7 ms, began
+        // after ~0.45 ms of copies); without the side walk, before
+        // k_lz_walk on the job's stream
+        if (lzf && j.raw_list) {
+            HIPCHK(c, raw_fork.open(s, c->side2, &lzf_fork));
+            STAGE("raw_copy", launch_raw_copy(j, c->side2.stream, cus));
+            HIPCHK(c, raw_fork.end());
+        } else {
+            STAGE("raw_copy", launch_raw_copy(j, s, cus));
         }
-        STAGE("lz_exec", launch_lz_exec(j, s));
-        // RPGPU_XXH_SIDE=0 (diagnostic build): the content checksums inside
-        // k_decode_finish, k_crc_compose and k_dchain in the validate stage (A/B)
-        static const bool xxh_side = [] { const char* e = diag_env("RPGPU_XXH_SIDE"); return !(e && *e == '0'); }();
-        xside = xxh_side;
-        // the gzip / zstd members first: k_zexec's workgroups take a CU's
-        // registers each and did not fit beside k_content_xxh's waves
-        STAGE("inflate", launch_inflate(j, s, c->cu_count * 4));
-        STAGE("zexec", launch_zexec(j, s));
-        STAGE("zexact", launch_zexact(j, s, 1));
-        if (c->hc_n) STAGE("host_scatter", launch_host_scatter(j, (const HostItem*)c->hc_items.p, c->hc_n,
-                                                               (const uint8_t*)c->hc_out.p, s));
-        if (xside) {
-            // k_crc_compose (no dependence on the decoded bytes) before the
-            // fork, for the same reason.  Then the LZ4F content checksums
-            // (serial XXH32 chains, ~1 ms per MiB on one wave each: the rest
-            // of the chip idles) on the side stream beside k_decode_finish
-            // and the decoded payloads' record chains, which do not depend on
-            // them (k_decode_finish gives a checksummed frame its verdict as
-            // if it matched; k_content_apply takes it back after the join)
-            // RPGPU_COMPOSE_BESIDE=1 (diagnostic build): k_crc_compose after the
-            // fork, 8 waves per workgroup (room for a hashing wave per SIMD) (A/B)
-            static const bool compose_beside = [] { const char* e = diag_env("RPGPU_COMPOSE_BESIDE"); return e && *e == '1'; }();
-            if (!compose_beside) STAGE("crc_compose", launch_crc_compose(j, s, c->cu_count));
-            if (!c->side) HIPCHK(c, side_stream_create(&c->side));
-            if (!c->fork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-            if (!c->join_ev) HIPCHK(c, hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming));
-            HIPCHK(c, hipEventRecord(c->fork_ev, s));
-            HIPCHK(c, hipStreamWaitEvent(c->side, c->fork_ev, 0));
-            xjoin.s = s;
-            xjoin.ev = c->join_ev;
-            xjoin.side = c->side;
-            STAGE("content_xxh", launch_content_xxh(j, c->side, c->cu_count * 2));
-            if (compose_beside) STAGE("crc_compose", launch_crc_compose(j, s, c->cu_count, 8));
-        }
-        STAGE("decode_finish", launch_decode_finish(j, s, c->cu_count * 8, xside));
-        if (xside) {
-            STAGE("dchain", launch_dchain(j, s, c->cu_count));
-            HIPCHK(c, hipEventRecord(c->join_ev, c->side));
-            HIPCHK(c, hipStreamWaitEvent(s, c->join_ev, 0));
-            xjoin.side = nullptr;  // joined
-            STAGE("content_apply", launch_content_apply(j, s, c->cu_count));
-        }
+        STAGE("lz_walk", launch_lz_walk(j, s, diag().lzwalk_wgs ? diag().lzwalk_wgs : cus * 16));
+        HIPCHK(c, lzf_fork.join());
+        HIPCHK(c, raw_fork.join());
     }
-    // RPGPU_WALK_WGS (diagnostic build): k_walk's grid (workgroups per CU)
-    static const uint32_t walk_wgs = [] { const char* e = diag_env("RPGPU_WALK_WGS"); return e ? (uint32_t)atoi(e) : 8u; }();
-    if (tm) HIPCHK(c, hipEventRecord(ev[3], s));
-    STAGE("validate", launch_validate(j, s, c->cu_count, !xside));
+    STAGE("lz_exec", launch_lz_exec(j, s));
+    // the gzip / zstd members first: k_zexec's workgroups take a CU's
+    // registers each and did not fit beside k_content_xxh's waves
+    STAGE("inflate", launch_inflate(j, s, cus * 4));
+    STAGE("zexec", launch_zexec(j, s));
+    STAGE("zexact", launch_zexact(j, s, 1));
+    if (c->hc_n) STAGE("host_scatter", launch_host_scatter(j, c->hc_items.as<const HostItem>(), c->hc_n,
+                                                           c->hc_out.as<const uint8_t>(), s));
+    Fork xfork;
+    if (xside) {
+        // k_crc_compose (no dependence on the decoded bytes) before the
+        // fork, for the same reason.  Then the LZ4F content checksums
+        // (serial XXH32 chains, ~1 ms per MiB on one wave each: the rest
+        // of the chip idles) on the side stream beside k_decode_finish
+        // and the decoded payloads' record chains, which do not depend on
+        // them (k_decode_finish gives a checksummed frame its verdict as
+        // if it matched; k_content_apply takes it back after the join)
+        STAGE("crc_compose", launch_crc_compose(j, s, cus));
+        HIPCHK(c, xfork.open(s, c->side));
+        STAGE("content_xxh", launch_content_xxh(j, c->side.stream, cus * 2));
+    }
+    STAGE("decode_finish", launch_decode_finish(j, s, cus * 8, xside));
+    if (xside) {
+        STAGE("dchain", launch_dchain(j, s, cus));
+        HIPCHK(c, xfork.join());
+        STAGE("content_apply", launch_content_apply(j, s, cus));
+    }
+    return RPGPU_OK;
+}
+
+// validate -> walk -> finalize.  xside: k_crc_compose and k_dchain already
+// ran in the decode stage.
+int stage_validate(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s, hipEvent_t* ev, bool xside) {
+    const uint32_t cus = c->cu_count;
+    STAGE("validate", launch_validate(j, s, cus, !xside));
     // the decoded payloads' record chains, then their walk.  (k_dchain on the
     // side stream beside k_crc_compose / k_validate measured slower than here:
     // C2 validate stage 4.36 against 3.72 ms, the chains' serial loads
     // queueing behind the two streams' HBM traffic)
-    if (!xside) STAGE("dchain", launch_dchain(j, s, c->cu_count));
-    STAGE("validate_decoded", launch_validate_decoded(j, s, c->cu_count));
-    if (tm) HIPCHK(c, hipEventRecord(ev[4], s));
-    STAGE("walk", launch_walk(j, s, c->cu_count * walk_wgs));
-    if (tm) HIPCHK(c, hipEventRecord(ev[5], s));
+    if (!xside) STAGE("dchain", launch_dchain(j, s, cus));
+    STAGE("validate_decoded", launch_validate_decoded(j, s, cus));
+    HIPCHK(c, mark(ev, 4, s));
+    STAGE("walk", launch_walk(j, s, cus * diag().walk_wgs));
+    HIPCHK(c, mark(ev, 5, s));
     STAGE("finalize", launch_finalize(j, s));
-    if (tm) HIPCHK(c, hipEventRecord(ev[6], s));
-#undef STAGE
+    HIPCHK(c, mark(ev, 6, s));
     return RPGPU_OK;
+}
+#undef STAGE
+
+int submit_body(rpgpu_ctx* c, const rpgpu_job* job, hipStream_t s, int stop, PlanPtrs* plan) {
+    if (int rc = check_job(c, job)) return rc;
+    const Layout L = job_layout(job, c->cu_count);
+    if (L.tc > 0xFFFFFFF0ull) return fail(c, RPGPU_E_INVALID, "rpgpu_submit: too many chunks");
+    DeviceJob j;
+    if (int rc = bind_job(c, job, L, s, stop, j)) return rc;
+    uint64_t* scan_tmp = (uint64_t*)(c->ws.as<uint8_t>() + L.scan);
+    if (plan) {
+        plan->n_batches = j.chunk_count + L.tc;
+        plan->slots = j.slots;
+        plan->dcap = j.dcap;
+    }
+    // timed submits only: rpgpu_query_capacity's planning runs stop early
+    // and record no timings
+    hipEvent_t* ev = nullptr;
+    if (c->timing && stop == kRunAll) {
+        if (c->ev_used == c->ev_sets.size()) {
+            std::array<hipEvent_t, 7> set;
+            for (auto& e : set) HIPCHK(c, hipEventCreate(&e));
+            c->ev_sets.push_back(set);
+        }
+        ev = c->ev_sets[c->ev_used++].data();
+        HIPCHK(c, mark(ev, 0, s));
+    }
+    if (int rc = stage_discover(c, j, s, ev, scan_tmp, stop != kStopAfterCount)) return rc;
+    if (stop == kStopAfterCount) return RPGPU_OK;
+    if (int rc = stage_members(c, j, s, scan_tmp)) return rc;
+    if (stop == kStopAfterPlan) return RPGPU_OK;
+    HIPCHK(c, mark(ev, 2, s));
+    const bool dec = (j.flags & RPGPU_JOB_DECODE) && j.decoded;
+    const bool xside = dec && diag().xxh_side;
+    if (dec)
+        if (int rc = stage_decode(c, j, s, xside)) return rc;
+    HIPCHK(c, mark(ev, 3, s));
+    return stage_validate(c, j, s, ev, xside);
 }
 }  // namespace
 
@@ -1168,25 +1160,17 @@ int rpgpu_query_capacity(rpgpu_ctx* c, const rpgpu_job* job, void* stream, rpgpu
     hipSetDevice(c->device);
     hipStream_t s = pick(c, stream);
     const uint32_t nseg = job->n_segments;
-    auto grow = [&](void** p, size_t* have, size_t want) -> int {
-        if (want <= *have) return RPGPU_OK;
-        if (*p) {
-            if (int rc = ws_drain(c, s)) return rc;
-            HIPCHK(c, hipFree(*p));
-            *p = nullptr;
-            *have = 0;
-        }
-        if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; return fail(c, RPGPU_E_NOMEM, "rpgpu_query_capacity: scratch"); }
-        *have = want;
-        return RPGPU_OK;
-    };
     const size_t fixed = align_up((size_t)nseg * sizeof(rpgpu_segment_summary), 256) + align_up(sizeof(rpgpu_job_totals), 256);
-    int rc = grow(&c->qws, &c->qws_bytes, fixed + 256);
+    int rc = grow(c, c->qws, fixed + 256, s, "rpgpu_query_capacity: scratch");
     if (rc) return rc;
     rpgpu_job q = *job;
-    q.d_summaries = (rpgpu_segment_summary*)c->qws;
-    q.d_totals = (rpgpu_job_totals*)((uint8_t*)c->qws + align_up((size_t)nseg * sizeof(rpgpu_segment_summary), 256));
-    q.d_batches = (rpgpu_batch_result*)((uint8_t*)c->qws + fixed);
+    auto point = [&] {
+        uint8_t* w = c->qws.as<uint8_t>();
+        q.d_summaries = (rpgpu_segment_summary*)w;
+        q.d_totals = (rpgpu_job_totals*)(w + align_up((size_t)nseg * sizeof(rpgpu_segment_summary), 256));
+        q.d_batches = (rpgpu_batch_result*)(w + fixed);
+    };
+    point();
     q.batch_capacity = 0;
     q.d_records = nullptr;
     q.record_capacity = 0;
@@ -1199,11 +1183,9 @@ int rpgpu_query_capacity(rpgpu_ctx* c, const rpgpu_job* job, void* stream, rpgpu
     uint64_t nb = 0;
     HIPCHK(c, hipMemcpyAsync(&nb, pp.n_batches, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    rc = grow(&c->qws, &c->qws_bytes, fixed + (size_t)(nb + 1) * sizeof(rpgpu_batch_result));
+    rc = grow(c, c->qws, fixed + (size_t)(nb + 1) * sizeof(rpgpu_batch_result), s, "rpgpu_query_capacity: scratch");
     if (rc) return rc;
-    q.d_summaries = (rpgpu_segment_summary*)c->qws;
-    q.d_totals = (rpgpu_job_totals*)((uint8_t*)c->qws + align_up((size_t)nseg * sizeof(rpgpu_segment_summary), 256));
-    q.d_batches = (rpgpu_batch_result*)((uint8_t*)c->qws + fixed);
+    point();
     q.batch_capacity = nb;
     rc = submit_impl(c, &q, stream, kStopAfterPlan, &pp);
     if (rc) return rc;
@@ -1306,28 +1288,18 @@ int rpgpu_segment_index(rpgpu_ctx* c, const rpgpu_batch_result* d_batches, uint6
     if (n_segments > 0x7FFFFFFFu) return fail(c, RPGPU_E_INVALID, "rpgpu_segment_index: too many segments");
     hipSetDevice(c->device);
     hipStream_t s = pick(c, stream);
-    // RPGPU_INDEX_SERIAL=1 (diagnostic build): the one-wave-per-segment walk (A/B reference)
-    static const bool serial = [] { const char* e = diag_env("RPGPU_INDEX_SERIAL"); return e && e[0] == '1'; }();
-    if (serial) {
+    if (diag().index_serial) {  // diagnostic build: the A/B reference
         HIPCHK(c, launch_segment_index(d_batches, batch_capacity, d_summaries, n_segments, step, d_states, d_rel_offset,
                                        d_rel_time, d_position, s));
         return RPGPU_OK;
     }
-    const size_t need = segment_index_ws_bytes(n_segments, batch_capacity);
-    if (need > c->iws_bytes) {
-        if (c->iws) {
-            if (int rc = ws_drain(c, s)) return rc;  // the old tables may still be in use on another stream
-            HIPCHK(c, hipFree(c->iws));
-            c->iws = nullptr;
-            c->iws_bytes = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->iws, need));
-        c->iws_bytes = need;
-    }
-    if (int rc = ws_acquire(c, s)) return rc;
+    if (int rc = grow(c, c->iws, segment_index_ws_bytes(n_segments, batch_capacity), s, "rpgpu_segment_index workspace"))
+        return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
     HIPCHK(c, launch_segment_index_pieces(d_batches, batch_capacity, d_summaries, n_segments, step, d_states,
-                                          d_rel_offset, d_rel_time, d_position, c->iws, s));
-    return ws_release(c, s);
+                                          d_rel_offset, d_rel_time, d_position, c->iws.p, s));
+    return scratch.release();
 }
 
 int rpgpu_uncompress(rpgpu_ctx* c, int codec, const void* in, size_t n, void* out, size_t cap, size_t* out_len) {
@@ -1345,12 +1317,8 @@ int rpgpu_uncompress(rpgpu_ctx* c, int codec, const void* in, size_t n, void* ou
     const uint64_t dcap = decode_capacity_dev(codec, (const uint8_t*)in, n);
     const size_t in_sz = align_up(n + 16, 256), out_sz = align_up(dcap + 16, 256);
     const size_t need = in_sz + out_sz + 256;
-    if (need > c->uws_bytes) {
-        if (c->uws) { hipStreamSynchronize(c->stream); hipFree(c->uws); c->uws = nullptr; }
-        if (hipMalloc(&c->uws, need) != hipSuccess) { c->uws_bytes = 0; return fail(c, RPGPU_E_NOMEM, "uncompress workspace"); }
-        c->uws_bytes = need;
-    }
-    uint8_t* d_in = (uint8_t*)c->uws;
+    if (int rc = grow(c, c->uws, need, c->stream, "uncompress workspace")) return rc;
+    uint8_t* d_in = c->uws.as<uint8_t>();
     uint8_t* d_out = d_in + in_sz;
     int64_t* d_res = (int64_t*)(d_out + out_sz);
     HIPCHK(c, hipMemsetAsync(d_in + n, 0, in_sz - n, c->stream));
@@ -1380,18 +1348,10 @@ int rpgpu_stamp(rpgpu_ctx* c, uint8_t* d_data, const uint64_t* d_pos, const uint
     hipStream_t s = pick(c, stream);
     const size_t o_steps = 0, o_scan = align_up((size_t)(n + 1) * 8, 256);
     const size_t o_cur = align_up(o_scan + scan_temp_bytes(n) + 64, 256), need = o_cur + 256;
-    if (need > c->sws_bytes) {
-        if (c->sws) {
-            if (int rc = ws_drain(c, s)) return rc;
-            HIPCHK(c, hipFree(c->sws));
-            c->sws = nullptr;
-            c->sws_bytes = 0;
-        }
-        if (hipMalloc(&c->sws, need) != hipSuccess) { c->sws = nullptr; return fail(c, RPGPU_E_NOMEM, "rpgpu_stamp workspace"); }
-        c->sws_bytes = need;
-    }
-    if (int rc = ws_acquire(c, s)) return rc;
-    uint8_t* w = (uint8_t*)c->sws;
+    if (int rc = grow(c, c->sws, need, s, "rpgpu_stamp workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->sws.as<uint8_t>();
     uint64_t* steps = (uint64_t*)(w + o_steps);
     uint32_t* cursor = (uint32_t*)(w + o_cur);
     HIPCHK(c, hipMemsetAsync(cursor, 0, 4, s));
@@ -1400,7 +1360,7 @@ int rpgpu_stamp(rpgpu_ctx* c, uint8_t* d_data, const uint64_t* d_pos, const uint
         HIPCHK(c, scan_exclusive_u64(steps, n, w + o_scan, scan_temp_bytes(n) + 64, s));
     }
     HIPCHK(c, launch_stamp(d_data, d_pos, d_payload_len, steps, next_offset, n, flags, c->d_tables, cursor, c->cu_count, s));
-    return ws_release(c, s);
+    return scratch.release();
 }
 
 // Key compaction over a completed job's outputs (kernels in rp_compact.hip).
@@ -1438,31 +1398,17 @@ int rpgpu_compact(rpgpu_ctx* c, const rpgpu_compact_job* job, void* stream) {
     const size_t o_bpos = take((nb + 1) * 8), o_bcnt = take((nb + 1) * 8), o_bkept = take(nb * 4), o_bplen = take(nb * 4);
     const size_t o_spos = take(nb * 8), o_splen = take(nb * 4), o_scan = take(scan_temp_bytes(nb) + 64), o_cnt = take(256);
     need += 256;
-    if (need > c->cws_bytes) {
-        if (c->cws) {
-            if (int rc = ws_drain(c, s)) return rc;
-            HIPCHK(c, hipFree(c->cws));
-            c->cws = nullptr;
-            c->cws_bytes = 0;
-        }
-        if (hipMalloc(&c->cws, need) != hipSuccess) { c->cws = nullptr; return fail(c, RPGPU_E_NOMEM, "rpgpu_compact workspace"); }
-        c->cws_bytes = need;
-    }
-    if (int rc = ws_acquire(c, s)) return rc;
-    uint8_t* w = (uint8_t*)c->cws;
+    if (int rc = grow(c, c->cws, need, s, "rpgpu_compact workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->cws.as<uint8_t>();
     CompactArgs a;
     a.job = *job;
     a.nb = nb;
     a.nr = nr;
     a.table = (uint64_t*)(w + o_table);
     a.table_mask = words - 1;
-    a.tag_mask = ~0u;
-    // RPGPU_CKEY_TAG_BITS=n (diagnostic build): n tag bits, and probes start at the tag, so that
-    // different keys meet on one tag
-    if (const char* e = diag_env("RPGPU_CKEY_TAG_BITS")) {
-        const int bits = atoi(e);
-        if (bits >= 0 && bits < 32) a.tag_mask = (1u << bits) - 1u;
-    }
+    a.tag_mask = diag().ckey_tag_mask;  // diagnostic build: few tag bits, so that different keys meet on one tag
     a.seg_state = (uint32_t*)(w + o_state);
     a.seg_acc = (uint64_t*)(w + o_acc);
     a.bpos = (uint64_t*)(w + o_bpos);
@@ -1508,7 +1454,7 @@ int rpgpu_compact(rpgpu_ctx* c, const rpgpu_compact_job* job, void* stream) {
                                a.counters + 2, c->cu_count, s, a.counters + 1));
     HIPCHK(c, mark(5));
     c->cev_live = timed;
-    return ws_release(c, s);
+    return scratch.release();
 }
 
 int rpgpu_compact_timings(rpgpu_ctx* c, float* ms, int n) {
@@ -1536,28 +1482,20 @@ int rpgpu_serialize_wire(rpgpu_ctx* c, const uint8_t* d_data, const uint64_t* d_
     hipStream_t s = pick(c, stream);
     const size_t o_dst = align_up((size_t)(n + 1) * 8, 256), o_scan = o_dst + align_up((size_t)(n + 1) * 8, 256);
     const size_t need = o_scan + scan_temp_bytes(n) + 256;
-    if (need > c->sws_bytes) {
-        if (c->sws) {
-            if (int rc = ws_drain(c, s)) return rc;
-            HIPCHK(c, hipFree(c->sws));
-            c->sws = nullptr;
-            c->sws_bytes = 0;
-        }
-        if (hipMalloc(&c->sws, need) != hipSuccess) { c->sws = nullptr; return fail(c, RPGPU_E_NOMEM, "rpgpu_serialize_wire workspace"); }
-        c->sws_bytes = need;
-    }
-    if (int rc = ws_acquire(c, s)) return rc;
-    uint8_t* w = (uint8_t*)c->sws;
+    if (int rc = grow(c, c->sws, need, s, "rpgpu_serialize_wire workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->sws.as<uint8_t>();
     uint64_t* src = (uint64_t*)w;
     uint64_t* dst = (uint64_t*)(w + o_dst);
     if (n == 0) {
         HIPCHK(c, hipMemsetAsync(d_total, 0, 8, s));
-        return ws_release(c, s);
+        return scratch.release();
     }
     HIPCHK(c, launch_to_wire(d_data, d_wire, d_batches, d_seg_offsets, first, n, src, dst, w + o_scan,
                              scan_temp_bytes(n) + 64, c->cu_count * 8, s));
     HIPCHK(c, hipMemcpyAsync(d_total, dst + n, 8, hipMemcpyDeviceToDevice, s));
-    return ws_release(c, s);
+    return scratch.release();
 }
 
 // Many payloads per GPU round trip (the per-batch call sites of
@@ -1602,18 +1540,10 @@ int rpgpu_uncompress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const vo
     // first three parts, then the outputs coming back
     const size_t o_items = align_up(in_total + 16, 256), o_res = align_up(o_items + m * sizeof(UncItem), 256);
     const size_t o_out = align_up(o_res + (size_t)m * 16, 256), total = o_out + out_total;
-    if (total > c->bd_bytes) {
-        if (c->bd) { HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipFree(c->bd)); c->bd = nullptr; c->bd_bytes = 0; }
-        if (hipMalloc(&c->bd, total) != hipSuccess) { c->bd = nullptr; return fail(c, RPGPU_E_NOMEM, "uncompress batch staging"); }
-        c->bd_bytes = total;
-    }
-    if (total > c->bh_bytes) {
-        if (c->bh) { HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipHostFree(c->bh)); c->bh = nullptr; c->bh_bytes = 0; }
-        if (hipHostMalloc(&c->bh, total, hipHostMallocDefault) != hipSuccess) { c->bh = nullptr; return fail(c, RPGPU_E_NOMEM, "uncompress batch pinned staging"); }
-        c->bh_bytes = total;
-    }
-    uint8_t* h = (uint8_t*)c->bh;
-    uint8_t* d = (uint8_t*)c->bd;
+    if (int rc = grow(c, c->bd, total, s, "uncompress batch staging")) return rc;
+    if (int rc = grow(c, c->bh, total, s, "uncompress batch pinned staging")) return rc;
+    uint8_t* h = c->bh.as<uint8_t>();
+    uint8_t* d = c->bd.as<uint8_t>();
     std::memset(h + in_total, 0, o_items - in_total);
     for (uint32_t k = 0; k < m; k++) std::memcpy(h + items[k].src, in[dev[k]], items[k].n);
     std::memcpy(h + o_items, items.data(), m * sizeof(UncItem));
@@ -1731,18 +1661,10 @@ int rpgpu_compress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const void
     const size_t o_len = align_up(o_pay + (size_t)np * sizeof(CompPayload), 256);
     const size_t o_sz = align_up(o_len + (size_t)np * 8, 256), o_out = align_up(o_sz + (size_t)nb * 4, 256);
     const size_t o_scr = align_up(o_out + out_total, 256), total = o_scr + (size_t)nb * kCompSlot;
-    if (total > c->bd_bytes) {
-        if (c->bd) { HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipFree(c->bd)); c->bd = nullptr; c->bd_bytes = 0; }
-        if (hipMalloc(&c->bd, total) != hipSuccess) { c->bd = nullptr; return fail(c, RPGPU_E_NOMEM, "compress staging"); }
-        c->bd_bytes = total;
-    }
-    if (o_scr > c->bh_bytes) {
-        if (c->bh) { HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipHostFree(c->bh)); c->bh = nullptr; c->bh_bytes = 0; }
-        if (hipHostMalloc(&c->bh, o_scr, hipHostMallocDefault) != hipSuccess) { c->bh = nullptr; return fail(c, RPGPU_E_NOMEM, "compress pinned staging"); }
-        c->bh_bytes = o_scr;
-    }
-    uint8_t* h = (uint8_t*)c->bh;
-    uint8_t* d = (uint8_t*)c->bd;
+    if (int rc = grow(c, c->bd, total, s, "compress staging")) return rc;
+    if (int rc = grow(c, c->bh, o_scr, s, "compress pinned staging")) return rc;
+    uint8_t* h = c->bh.as<uint8_t>();
+    uint8_t* d = c->bd.as<uint8_t>();
     std::memset(h, 0, o_blk);
     for (const Stage& st : stage)
         if (st.n) std::memcpy(h + st.off, st.src, st.n);
@@ -1789,18 +1711,13 @@ uint64_t host_group_bytes(const rpgpu_host_job* job) {
     return job->group_kib ? (uint64_t)job->group_kib << 10 : kHostGroupBytes;
 }
 
+// a slot's staging for n elements of T (its capacity is count<T>())
 template <class T>
-int grow(rpgpu_ctx* c, T*& p, uint64_t& have, uint64_t need) {
-    if (need <= have && p) return RPGPU_OK;
-    // hipFree waits for the device work still using the old buffer
-    if (p) hipFree(p);
-    p = nullptr;
-    have = 0;
-    if (hipMalloc((void**)&p, (size_t)std::max<uint64_t>(need, 1) * sizeof(T)) != hipSuccess)
-        return fail(c, RPGPU_E_NOMEM, "rpgpu_validate_host: device staging");
-    have = need;
-    return RPGPU_OK;
+int slot_grow(rpgpu_ctx* c, Buf& b, uint64_t n) {
+    return grow(c, b, (size_t)std::max<uint64_t>(n, 1) * sizeof(T), c->stream, "rpgpu_validate_host: device staging");
 }
+template <class T>
+uint64_t count(const Buf& b) { return b.bytes / sizeof(T); }
 
 struct HostGroup {
     uint32_t seg0, nseg;
@@ -1811,65 +1728,61 @@ struct HostGroup {
 // compute stream (after the copy), then the totals back to pinned memory
 int host_issue(rpgpu_ctx* c, rpgpu_ctx::HostSlot& h, const rpgpu_host_job* job, const HostGroup& g) {
     const uint64_t padded = align_up(g.bytes + 64, 256);
-    if (int rc = grow(c, h.d_data, h.data_bytes, padded)) return rc;
-    if (int rc = grow(c, h.d_offs, h.offs_n, (uint64_t)g.nseg + 1)) return rc;
-    if (int rc = grow(c, h.d_sums, h.sums_n, (uint64_t)g.nseg)) return rc;
+    if (int rc = slot_grow<uint8_t>(c, h.d_data, padded)) return rc;
+    if (int rc = slot_grow<uint64_t>(c, h.d_offs, (uint64_t)g.nseg + 1)) return rc;
+    if (int rc = slot_grow<rpgpu_segment_summary>(c, h.d_sums, (uint64_t)g.nseg)) return rc;
     // first-try capacities: every batch at least a header, every record at
     // least 7 bytes (length, attributes, three deltas/lengths, header count),
     // decode up to 4x; a group that overflows is re-run
     const uint64_t bneed = g.bytes / RPGPU_HEADER_SIZE + 1;
-    if (int rc = grow(c, h.d_batches, h.bcap, bneed)) return rc;
+    if (int rc = slot_grow<rpgpu_batch_result>(c, h.d_batches, bneed)) return rc;
     if (job->flags & RPGPU_JOB_PARSE)
-        if (int rc = grow(c, h.d_records, h.rcap, g.bytes / 7 + 1)) return rc;
+        if (int rc = slot_grow<rpgpu_record_index>(c, h.d_records, g.bytes / 7 + 1)) return rc;
     if (job->flags & RPGPU_JOB_DECODE)
-        if (int rc = grow(c, h.d_decoded, h.dcap, 4 * g.bytes + 4096)) return rc;
+        if (int rc = slot_grow<uint8_t>(c, h.d_decoded, 4 * g.bytes + 4096)) return rc;
     h.h_offs.assign(g.nseg + 1, 0);
     for (uint32_t i = 0; i < g.nseg; i++) h.h_offs[i + 1] = h.h_offs[i] + job->seg_sizes[g.seg0 + i];
     for (uint32_t i = 0; i < g.nseg; i++)
         if (job->seg_sizes[g.seg0 + i])
-            HIPCHK(c, hipMemcpyAsync(h.d_data + h.h_offs[i], job->segments[g.seg0 + i], job->seg_sizes[g.seg0 + i],
-                                     hipMemcpyHostToDevice, c->copy));
-    HIPCHK(c, hipMemcpyAsync(h.d_offs, h.h_offs.data(), (g.nseg + 1) * 8, hipMemcpyHostToDevice, c->copy));
+            HIPCHK(c, hipMemcpyAsync(h.d_data.as<uint8_t>() + h.h_offs[i], job->segments[g.seg0 + i],
+                                     job->seg_sizes[g.seg0 + i], hipMemcpyHostToDevice, c->copy));
+    HIPCHK(c, hipMemcpyAsync(h.d_offs.p, h.h_offs.data(), (g.nseg + 1) * 8, hipMemcpyHostToDevice, c->copy));
     HIPCHK(c, hipEventRecord(h.h2d, c->copy));
     HIPCHK(c, hipStreamWaitEvent(c->stream, h.h2d, 0));
+    const uint64_t bcap = count<rpgpu_batch_result>(h.d_batches);
     rpgpu_job j{};
-    j.d_data = h.d_data;
-    j.d_seg_offsets = h.d_offs;
+    j.d_data = h.d_data.as<uint8_t>();
+    j.d_seg_offsets = h.d_offs.as<uint64_t>();
     j.h_seg_offsets = h.h_offs.data();
     j.n_segments = g.nseg;
     j.layout = job->layout;
     j.flags = job->flags;
-    j.d_batches = h.d_batches;
-    j.batch_capacity = h.bcap;
-    j.d_records = h.d_records;
-    j.record_capacity = (job->flags & RPGPU_JOB_PARSE) ? h.rcap : 0;
-    j.d_decoded = h.d_decoded;
-    j.decoded_capacity = (job->flags & RPGPU_JOB_DECODE) ? h.dcap : 0;
-    j.d_summaries = h.d_sums;
-    j.d_totals = h.d_tot;
+    j.d_batches = h.d_batches.as<rpgpu_batch_result>();
+    j.batch_capacity = bcap;
+    j.d_records = h.d_records.as<rpgpu_record_index>();
+    j.record_capacity = (job->flags & RPGPU_JOB_PARSE) ? count<rpgpu_record_index>(h.d_records) : 0;
+    j.d_decoded = h.d_decoded.as<uint8_t>();
+    j.decoded_capacity = (job->flags & RPGPU_JOB_DECODE) ? h.d_decoded.bytes : 0;
+    j.d_summaries = h.d_sums.as<rpgpu_segment_summary>();
+    j.d_totals = h.d_tot.as<rpgpu_job_totals>();
     if (int rc = rpgpu_submit(c, &j, c->stream)) return rc;
     if (job->index_step && job->layout == RPGPU_LAYOUT_DISK) {
         // segment_index::maybe_track over the group's crc-good prefixes
         // (storage/log_replayer.cc:62-74), base offsets from the caller
-        if (int rc = grow(c, h.d_ist, h.ist_n, (uint64_t)g.nseg)) return rc;
-        if (h.ix_n < h.bcap || !h.d_ro) {
-            uint64_t have = 0;
-            if (int rc = grow(c, h.d_ro, have, h.bcap)) return rc;
-            have = 0;
-            if (int rc = grow(c, h.d_rt, have, h.bcap)) return rc;
-            have = 0;
-            if (int rc = grow(c, h.d_ps, have, h.bcap)) return rc;
-            h.ix_n = h.bcap;
-        }
+        if (int rc = slot_grow<rpgpu_index_state>(c, h.d_ist, (uint64_t)g.nseg)) return rc;
+        if (int rc = slot_grow<uint32_t>(c, h.d_ro, bcap)) return rc;
+        if (int rc = slot_grow<uint32_t>(c, h.d_rt, bcap)) return rc;
+        if (int rc = slot_grow<uint64_t>(c, h.d_ps, bcap)) return rc;
         h.h_ist.assign(g.nseg, rpgpu_index_state{});
         for (uint32_t i = 0; i < g.nseg; i++) h.h_ist[i].base_offset = job->index_states[g.seg0 + i].base_offset;
-        HIPCHK(c, hipMemcpyAsync(h.d_ist, h.h_ist.data(), g.nseg * sizeof(rpgpu_index_state), hipMemcpyHostToDevice,
+        HIPCHK(c, hipMemcpyAsync(h.d_ist.p, h.h_ist.data(), g.nseg * sizeof(rpgpu_index_state), hipMemcpyHostToDevice,
                                  c->stream));
-        if (int rc = rpgpu_segment_index(c, h.d_batches, h.bcap, h.d_sums, g.nseg, job->index_step, h.d_ist, h.d_ro, h.d_rt,
-                                         h.d_ps, c->stream))
+        if (int rc = rpgpu_segment_index(c, j.d_batches, bcap, j.d_summaries, g.nseg, job->index_step,
+                                         h.d_ist.as<rpgpu_index_state>(), h.d_ro.as<uint32_t>(), h.d_rt.as<uint32_t>(),
+                                         h.d_ps.as<uint64_t>(), c->stream))
             return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(h.h_tot, h.d_tot, sizeof(rpgpu_job_totals), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.h_tot.p, h.d_tot.p, sizeof(rpgpu_job_totals), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(h.done, c->stream));
     return RPGPU_OK;
 }
@@ -1894,8 +1807,8 @@ int rpgpu_validate_host(rpgpu_ctx* c, const rpgpu_host_job* job) {
     for (auto& h : c->hs) {
         if (!h.h2d) HIPCHK(c, hipEventCreateWithFlags(&h.h2d, hipEventDisableTiming));
         if (!h.done) HIPCHK(c, hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
-        if (!h.h_tot) HIPCHK(c, hipHostMalloc((void**)&h.h_tot, sizeof(rpgpu_job_totals), hipHostMallocDefault));
-        if (!h.d_tot) HIPCHK(c, hipMalloc((void**)&h.d_tot, sizeof(rpgpu_job_totals)));
+        if (int rc = slot_grow<rpgpu_job_totals>(c, h.h_tot, 1)) return rc;
+        if (int rc = slot_grow<rpgpu_job_totals>(c, h.d_tot, 1)) return rc;
     }
     std::vector<HostGroup> groups;
     const uint64_t gbytes = host_group_bytes(job);
@@ -1914,17 +1827,18 @@ int rpgpu_validate_host(rpgpu_ctx* c, const rpgpu_host_job* job) {
         auto& h = c->hs[gi & 1];
         const HostGroup& g = groups[gi];
         HIPCHK(c, hipEventSynchronize(h.done));
-        for (int tries = 0; h.h_tot->overflow && tries < 2; tries++) {
-            const rpgpu_job_totals t = *h.h_tot;
-            if (int rc = grow(c, h.d_batches, h.bcap, t.batch_capacity_needed)) return rc;
+        const rpgpu_job_totals* h_tot = h.h_tot.as<rpgpu_job_totals>();
+        for (int tries = 0; h_tot->overflow && tries < 2; tries++) {
+            const rpgpu_job_totals t = *h_tot;
+            if (int rc = slot_grow<rpgpu_batch_result>(c, h.d_batches, t.batch_capacity_needed)) return rc;
             if (job->flags & RPGPU_JOB_PARSE)
-                if (int rc = grow(c, h.d_records, h.rcap, t.record_capacity_needed)) return rc;
+                if (int rc = slot_grow<rpgpu_record_index>(c, h.d_records, t.record_capacity_needed)) return rc;
             if (job->flags & RPGPU_JOB_DECODE)
-                if (int rc = grow(c, h.d_decoded, h.dcap, t.decoded_capacity_needed)) return rc;
+                if (int rc = slot_grow<uint8_t>(c, h.d_decoded, t.decoded_capacity_needed)) return rc;
             if (int rc = host_issue(c, h, job, g)) return rc;
             HIPCHK(c, hipEventSynchronize(h.done));
         }
-        const rpgpu_job_totals t = *h.h_tot;
+        const rpgpu_job_totals t = *h_tot;
         const uint64_t nb = t.n_batches;
         const uint64_t room = job->batch_capacity > out_b ? job->batch_capacity - out_b : 0;
         const uint64_t take = std::min(nb, room);
@@ -1942,22 +1856,22 @@ int rpgpu_validate_host(rpgpu_ctx* c, const rpgpu_host_job* job) {
         // results back on the copy stream: the compute stream already holds
         // the next group's pipeline, which must not be waited for here
         if (take) {
-            HIPCHK(c, hipMemcpyAsync(job->batches + out_b, h.d_batches, take * sizeof(rpgpu_batch_result),
+            HIPCHK(c, hipMemcpyAsync(job->batches + out_b, h.d_batches.p, take * sizeof(rpgpu_batch_result),
                                      hipMemcpyDeviceToHost, c->copy));
             if (ix) {
-                HIPCHK(c, hipMemcpyAsync(job->rel_offset + out_b, h.d_ro, take * 4, hipMemcpyDeviceToHost, c->copy));
-                HIPCHK(c, hipMemcpyAsync(job->rel_time + out_b, h.d_rt, take * 4, hipMemcpyDeviceToHost, c->copy));
-                HIPCHK(c, hipMemcpyAsync(job->position + out_b, h.d_ps, take * 8, hipMemcpyDeviceToHost, c->copy));
+                HIPCHK(c, hipMemcpyAsync(job->rel_offset + out_b, h.d_ro.p, take * 4, hipMemcpyDeviceToHost, c->copy));
+                HIPCHK(c, hipMemcpyAsync(job->rel_time + out_b, h.d_rt.p, take * 4, hipMemcpyDeviceToHost, c->copy));
+                HIPCHK(c, hipMemcpyAsync(job->position + out_b, h.d_ps.p, take * 8, hipMemcpyDeviceToHost, c->copy));
             }
         }
         if (rtake)
-            HIPCHK(c, hipMemcpyAsync(job->records + rec_base, h.d_records, rtake * sizeof(rpgpu_record_index),
+            HIPCHK(c, hipMemcpyAsync(job->records + rec_base, h.d_records.p, rtake * sizeof(rpgpu_record_index),
                                      hipMemcpyDeviceToHost, c->copy));
-        if (dtake) HIPCHK(c, hipMemcpyAsync(job->decoded + dec_base, h.d_decoded, dtake, hipMemcpyDeviceToHost, c->copy));
-        HIPCHK(c, hipMemcpyAsync(job->summaries + g.seg0, h.d_sums, g.nseg * sizeof(rpgpu_segment_summary),
+        if (dtake) HIPCHK(c, hipMemcpyAsync(job->decoded + dec_base, h.d_decoded.p, dtake, hipMemcpyDeviceToHost, c->copy));
+        HIPCHK(c, hipMemcpyAsync(job->summaries + g.seg0, h.d_sums.p, g.nseg * sizeof(rpgpu_segment_summary),
                                  hipMemcpyDeviceToHost, c->copy));
         if (ix)
-            HIPCHK(c, hipMemcpyAsync(job->index_states + g.seg0, h.d_ist, g.nseg * sizeof(rpgpu_index_state),
+            HIPCHK(c, hipMemcpyAsync(job->index_states + g.seg0, h.d_ist.p, g.nseg * sizeof(rpgpu_index_state),
                                      hipMemcpyDeviceToHost, c->copy));
         HIPCHK(c, hipStreamSynchronize(c->copy));
         // group-relative -> job-wide ordinals and positions
@@ -2011,26 +1925,10 @@ int rpgpu_stamp_host(rpgpu_ctx* c, uint8_t* buf, size_t len, const uint64_t* pos
     // device: [batches + 16][pos][plen]; host (pinned): the same
     const size_t o_pos = align_up(len + 16, 256), o_len = align_up(o_pos + (size_t)n * 8, 256);
     const size_t total = align_up(o_len + (size_t)n * 4, 256);
-    if (total > c->std_bytes) {
-        if (c->std_) {
-            if (int rc = ws_drain(c, s)) return rc;
-            HIPCHK(c, hipFree(c->std_));
-            c->std_ = nullptr;
-            c->std_bytes = 0;
-        }
-        if (hipMalloc(&c->std_, total) != hipSuccess) { c->std_ = nullptr; return fail(c, RPGPU_E_NOMEM, "stamp staging"); }
-        c->std_bytes = total;
-    }
-    if (total > c->sth_bytes) {
-        if (c->sth) { HIPCHK(c, hipStreamSynchronize(s)); HIPCHK(c, hipHostFree(c->sth)); c->sth = nullptr; c->sth_bytes = 0; }
-        if (hipHostMalloc(&c->sth, total, hipHostMallocDefault) != hipSuccess) {
-            c->sth = nullptr;
-            return fail(c, RPGPU_E_NOMEM, "stamp pinned staging");
-        }
-        c->sth_bytes = total;
-    }
-    uint8_t* h = (uint8_t*)c->sth;
-    uint8_t* d = (uint8_t*)c->std_;
+    if (int rc = grow(c, c->std_, total, s, "stamp staging")) return rc;
+    if (int rc = grow(c, c->sth, total, s, "stamp pinned staging")) return rc;
+    uint8_t* h = c->sth.as<uint8_t>();
+    uint8_t* d = c->std_.as<uint8_t>();
     std::memcpy(h, buf, len);
     std::memset(h + len, 0, 16);
     std::memcpy(h + o_pos, pos, (size_t)n * 8);

@@ -145,8 +145,36 @@ def case_zstd_ring_wave():
     print(f"zstd_ring_wave ok: {len(got.batches)} batches, {int(np.sum(ok))} decoded")
 
 
+PATH_SWITCHES = ("RPGPU_XXH_SIDE", "RPGPU_CRC_COMPOSE", "RPGPU_DCHAIN", "RPGPU_GZS", "RPGPU_LZF")
+
+
+def case_path_switch():
+    """One of PATH_SWITCHES set to 0: the alternative path it selects
+    (content checksums inside k_decode_finish, k_validate streaming every
+    stored payload, k_validate_decoded chaining the records itself, every gzip
+    member serial, every LZ4 piece through the walk / exec kernels) gives the
+    oracle's results on a small job of every codec."""
+    from oracle import oracle as O
+    from redpanda_amd.engine import Engine
+    from tests.test_gpu_parity import assert_same, gen, run_both
+    off = [k for k in PATH_SWITCHES if os.environ.get(k) == "0"]
+    assert len(off) == 1, f"run with exactly one of {PATH_SWITCHES} set to 0"
+    O.build()
+    eng = Engine(0)
+    segs = [gen(None, 1 << 20, i, seed=0x5A0 + i, batch_bytes=0, min_batch=200, max_batch=200000,
+                weights=[2, 2, 2, 4, 2, 2], lz4_content_checksum_ppm=300000, lz4_linked_ppm=300000,
+                corrupt_payload_ppm=(30000 if i == 1 else 0)) for i in range(2)]
+    got, ref = run_both(eng, O, segs, flags=DFLAGS)
+    codec = ref.batches["attrs"] & 7
+    ok = (ref.batches["flags"] & abi.F_CODEC_OK) != 0
+    for cd in (abi.CODEC_GZIP, abi.CODEC_SNAPPY, abi.CODEC_LZ4, abi.CODEC_ZSTD):
+        assert np.any(ok & (codec == cd)), f"no decoded batch of codec {cd}"
+    assert_same(got, ref, DFLAGS)
+    print(f"path_switch {off[0]}=0 ok: {len(got.batches)} batches, {int(np.sum(ok))} decoded")
+
+
 CASES = {"small_pool": case_small_pool, "host_codec_missing": case_host_codec_missing, "small_frec": case_small_frec,
-         "zstd_ring_wave": case_zstd_ring_wave}
+         "zstd_ring_wave": case_zstd_ring_wave, "path_switch": case_path_switch}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()

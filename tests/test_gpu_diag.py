@@ -2,7 +2,8 @@
 (tests/diag_cases.py): the gzip / zstd first-pass pool exhausted by hostile
 ISIZE trailers, RPGPU_JOB_HOST_CODECS without a loadable libzstd, and the
 LZ4 fast-path record pool cut so that listed and walked blocks mix, zstd
-ring-mode members through the wave decoder alone."""
+ring-mode members through the wave decoder alone, and each alternative launch
+path a diagnostic switch still selects."""
 import os
 import subprocess
 import sys
@@ -40,3 +41,10 @@ def test_lz4_fast_pool_exhausted(cap):
 
 def test_zstd_ring_exact_wave_decoder():
     assert "zstd_ring_wave ok" in _run("zstd_ring_wave", RPGPU_ZS_FAST="0")
+
+
+@pytest.mark.parametrize("switch", ["RPGPU_XXH_SIDE", "RPGPU_CRC_COMPOSE", "RPGPU_DCHAIN", "RPGPU_GZS", "RPGPU_LZF"])
+def test_path_switch_off_matches_oracle(switch):
+    """The launch-path switches that stay: each alternative path
+    on one small job of every codec."""
+    assert f"path_switch {switch}=0 ok" in _run("path_switch", **{switch: "0"})

@@ -208,6 +208,40 @@ constexpr uint32_t kGzsMaxK = 256;     // chunks per member at most
 // job counters (DeviceJob::counters), zeroed per submit
 constexpr size_t kCounterBytes = 256;
 
+// Stored payloads with at most kLaneWalkMax records are walked one lane per
+// batch by k_walk; k_validate walks the rest (and decoded payloads) with the
+// wave-parallel walk.  (k_emit and the validate kernels must agree on it: an
+// experiment build that changes it rebuilds rp_kernels.hip and rp_validate.hip.)
+#ifndef RPGPU_LANE_WALK_MAX
+#define RPGPU_LANE_WALK_MAX 256
+#endif
+constexpr int32_t kLaneWalkMax = RPGPU_LANE_WALK_MAX;
+__host__ __device__ __forceinline__ bool lane_walked(uint32_t flags, uint32_t codec, int32_t rc) {
+    return (flags & RPGPU_F_COMPLETE) && codec == 0 && rc <= kLaneWalkMax;
+}
+
+// k_emit -> k_walk, 16 bytes per batch (contiguous across the lanes of a wave,
+// where the batch results are 128 bytes apart): the absolute payload start,
+// its length and the record count, or kNotLaneWalked where lane_walked() is
+// false (incomplete, compressed, more than kLaneWalkMax records).
+struct WalkDesc {
+    uint64_t start;
+    uint32_t n;
+    int32_t rc;
+};
+static_assert(sizeof(WalkDesc) == 16, "one dwordx4 per lane");
+constexpr int32_t kNotLaneWalked = 0x7FFFFFFF;
+static_assert(kLaneWalkMax < kNotLaneWalked, "the mark is no record count k_walk takes");
+
+// k_walk -> k_finalize_bitmap, 8 bytes per batch: the walk's verdict bits
+// (RPGPU_F_PARSED ..), records_parsed (<= kLaneWalkMax) and parse_err; 0 =
+// k_walk left the batch alone (its verdict is whoever else's).
+constexpr uint64_t kVerdictWalked = 1ull << 63;
+__host__ __device__ __forceinline__ uint64_t walk_verdict_pack(uint32_t flags, uint32_t parsed, uint32_t perr) {
+    return kVerdictWalked | ((uint64_t)(perr & 0x7Fu) << 56) | ((uint64_t)(parsed & 0xFFFFFFu) << 32) | flags;
+}
+static_assert(kLaneWalkMax <= 0xFFFFFF, "records_parsed field of the verdict");
+
 struct DeviceJob {
     const uint8_t* data;
     uint64_t data_len;            // bytes of d_data (= h_seg_offsets[n_segments])
@@ -303,6 +337,8 @@ struct DeviceJob {
     uint32_t gzs_items_cap;
     uint16_t* gzs_pool;           // decoded symbols of the chunks (bytes, or 256 + a window position)
     uint64_t gzs_pool_syms;
+    WalkDesc* walk_desc;          // batch_capacity: k_emit -> k_walk, what a lane needs to walk its batch
+    uint64_t* walk_verdict;       // batch_capacity: k_walk -> k_finalize_bitmap (walk_verdict_pack; PARSE jobs)
 };
 
 // one host-decoded batch (RPGPU_JOB_HOST_CODECS): its payload, the host's

@@ -7,7 +7,8 @@
 //   k_emit       walk again, write headers + plan      (storage/parser.cc:36-76)
 //   scan x2      index slots / decode-arena bytes
 //   k_validate   CRC32C + record walk per batch        (model/record_utils.cc:68-181)
-//   k_finalize   checkpoint, bitmap, totals            (storage/log_replayer.cc:62-79)
+//   k_walk       lane record walk (<= 256 records): descriptor in, verdict out
+//   k_finalize   checkpoint, verdict merge + bitmap, totals (storage/log_replayer.cc:62-79)
 //
 // Integer/byte work only: HBM-bound, no MFMA.  The CRC runs from LDS tables
 // replicated 32x so every lane reads its own bank (conflict-free ds_read_b32).
@@ -513,6 +514,18 @@ __global__ __launch_bounds__(256) void k_emit(DeviceJob j) {
     const uint32_t c57 = j.tables->c57;
     const bool wire = j.layout == RPGPU_LAYOUT_WIRE;
     uint64_t p = j.chunk_entry[g];
+    // k_walk's descriptors leave up to four at a time, when their 64-byte
+    // line is complete (or the chunk ends): stored one per batch, 16 bytes a
+    // few microseconds apart, each cost more than one write request
+    WalkDesc wq[4];
+    uint32_t wn = 0;
+    uint64_t wfirst = 0;
+    auto wflush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (k < wn) j.walk_desc[wfirst + k] = wq[k];
+        wn = 0;
+    };
     for (uint64_t i = 0; i < cnt; i++) {
 #ifdef RPGPU_CHECKED
         if (!(p < len)) {
@@ -596,7 +609,22 @@ __global__ __launch_bounds__(256) void k_emit(DeviceJob j) {
             r.reserved1 = praw;
             j.batches[ord] = r;
             j.slots[ord] = slots;
+            // (read without DECODE too: k_validate's descriptor load takes
+            // decoded_off from it)
             j.dcap[ord] = cap;
+            // k_walk's descriptor: its lanes read this, not the batch result
+            if (j.flags & RPGPU_JOB_PARSE) {
+                WalkDesc wd;
+                wd.start = r.index_base;
+                wd.n = (uint32_t)(h.size - (int32_t)RPGPU_HEADER_SIZE);
+                wd.rc = lane_walked(f, codec, rc) ? rc : kNotLaneWalked;
+                if (wn == 0) wfirst = ord;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++)
+                    if (k == wn) wq[k] = wd;
+                wn++;
+                if ((ord & 3u) == 3u) wflush();
+            }
             // decode work list for k_decode (order is irrelevant: every item
             // writes only its own batch and its own reserved arena slot)
             if (complete && decodable) j.decode_list[atomicAdd(&j.counters[2], 1u)] = (uint32_t)ord;
@@ -612,6 +640,7 @@ __global__ __launch_bounds__(256) void k_emit(DeviceJob j) {
         if (!complete) break;
         p += RPGPU_HEADER_SIZE + h.need;
     }
+    wflush();
 }
 
 // ---------------------------------------------------------------------------
@@ -772,14 +801,31 @@ DEV bool batch_valid(uint32_t f, uint32_t job_flags, uint32_t layout) {
     return true;
 }
 
-// one lane per batch, one wave per bitmap word (a ballot of the lanes)
+// one lane per batch, one wave per bitmap word (a ballot of the lanes).
+// PARSE jobs: k_walk's verdict (walk_verdict_pack, one dense 8-byte word per
+// batch) is merged into the batch result here, where its flags are loaded
+// anyway: the bits OR-ed in, records_parsed and parse_err stored (all three
+// in the result's second 64-byte half); the bitmap word is balloted from the
+// merged flags.  A batch k_walk left alone (verdict 0) keeps what it has.
 __global__ __launch_bounds__(256) void k_finalize_bitmap(DeviceJob j) {
     const uint64_t nb_total = j.chunk_count[j.total_chunks];
     const uint64_t nb = nb_total < j.batch_capacity ? nb_total : j.batch_capacity;
     const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if ((b & ~63ull) >= nb) return;  // whole wave past the end
-    const uint64_t word = __ballot(b < nb && batch_valid(j.batches[b].flags, j.flags, j.layout));
-    if ((threadIdx.x & 63) == 0) j.bitmap[b >> 6] = word;
+    uint32_t f = 0;
+    if (b < nb) {
+        rpgpu_batch_result* R = &j.batches[b];
+        f = R->flags;
+        const uint64_t v = (j.flags & RPGPU_JOB_PARSE) ? j.walk_verdict[b] : 0;
+        if (v & kVerdictWalked) {
+            f |= (uint32_t)v;
+            R->flags = f;
+            R->records_parsed = (uint32_t)(v >> 32) & 0xFFFFFFu;
+            R->parse_err = (uint8_t)((v >> 56) & 0x7Fu);
+        }
+    }
+    const uint64_t word = __ballot(b < nb && batch_valid(f, j.flags, j.layout));
+    if (j.bitmap && (threadIdx.x & 63) == 0) j.bitmap[b >> 6] = word;
 }
 
 __global__ void k_finalize_totals(DeviceJob j) {
@@ -943,7 +989,8 @@ hipError_t launch_emit(const DeviceJob& j, hipStream_t s) {
 hipError_t launch_finalize(const DeviceJob& j, hipStream_t s) {
     hipLaunchKernelGGL(k_finalize_segments, dim3(j.n_segments), dim3(256), 0, s, j);
     const uint64_t words = (j.batch_capacity + 63) / 64;
-    if (j.bitmap) {
+    // (without a bitmap output it still merges k_walk's verdicts)
+    if (j.bitmap || (j.flags & RPGPU_JOB_PARSE)) {
         const uint32_t grid = (uint32_t)((words * 64 + 255) / 256);
         hipLaunchKernelGGL(k_finalize_bitmap, dim3(grid ? grid : 1), dim3(256), 0, s, j);
     }

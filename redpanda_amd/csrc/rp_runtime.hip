@@ -716,6 +716,7 @@ struct Layout {
     size_t cbase, chunks, ccount, centry, segterm, slots, dcap, counters, dlist, slist, llist, fbad;
     size_t ilist, istate, ioff, itot, hlist, zitems, gzsmem, gzsit;
     size_t blocks, plans, pstate, longl, wlong, rawl, lanel, lzfl, lzft, split, spart, scan;
+    size_t wdesc, wverd;
     size_t need;
 };
 
@@ -782,6 +783,10 @@ Layout job_layout(const rpgpu_job* job, uint32_t cu_count) {
     L.split = take(L.split_cap * 4);
     L.spart = take(L.split_cap * kSplitParts * 4);
     L.scan = take(scan_temp_bytes(std::max<uint64_t>(tc, bcap)) + 64);
+    // k_emit -> k_walk descriptors and k_walk -> k_finalize_bitmap verdicts
+    const bool parse_job = (job->flags & RPGPU_JOB_PARSE) != 0;
+    L.wdesc = take(parse_job ? (bcap + 1) * sizeof(WalkDesc) : 0);
+    L.wverd = take(parse_job ? (bcap + 1) * 8 : 0);
     L.need = off;
     return L;
 }
@@ -928,6 +933,8 @@ int bind_job(rpgpu_ctx* c, const rpgpu_job* job, const Layout& L, hipStream_t s,
     j.blocks = (BlockItem*)(ws + L.blocks);
     j.block_capacity = (uint32_t)L.bl_cap;
     j.plans = (FramePlan*)(ws + L.plans);
+    j.walk_desc = (WalkDesc*)(ws + L.wdesc);
+    j.walk_verdict = (uint64_t*)(ws + L.wverd);
     if (((uintptr_t)job->d_decoded & 15) != 0) return fail(c, RPGPU_E_INVALID, "rpgpu_submit: d_decoded must be 16-byte aligned");
     return RPGPU_OK;
 }

@@ -713,16 +713,9 @@ DEV void note_bad(const DeviceJob& j, uint32_t seg, uint64_t b) {
     }
 }
 
-// Stored payloads with at most kLaneWalkMax records are walked one lane per
-// batch by k_walk; k_validate walks the rest (and decoded payloads) with the
-// wave-parallel walk.
-#ifndef RPGPU_LANE_WALK_MAX
-#define RPGPU_LANE_WALK_MAX 256
-#endif
-constexpr int32_t kLaneWalkMax = RPGPU_LANE_WALK_MAX;
-DEV bool lane_walked(uint32_t flags, uint32_t codec, int32_t rc) {
-    return (flags & RPGPU_F_COMPLETE) && codec == 0 && rc <= kLaneWalkMax;
-}
+// (lane_walked(), rp_internal.h: the stored payloads k_walk walks one lane
+// per batch; k_validate walks the rest, and decoded payloads, with the
+// wave-parallel walk.)
 
 // Per-batch descriptor, loaded one iteration ahead as ONE VGPR: lane i < 32
 // holds dword i of the batch result, lanes 32..37 the index-slot and
@@ -1165,34 +1158,38 @@ struct WalkCtx {
     const uint64_t* chunk_count;  // note_bad (wire only)
     const uint64_t* chunk_base;
     uint32_t* seg_first_bad;
+    const WalkDesc* desc;
+    uint64_t* verdict;
 };
 
 DEV WalkCtx walk_ctx(const DeviceJob& j) {
     return WalkCtx{j.data, j.seg_off, j.batches, j.slots, j.records, j.record_capacity, j.counters,
-                   j.chunk_count, j.chunk_base, j.seg_first_bad};
+                   j.chunk_count, j.chunk_base, j.seg_first_bad, j.walk_desc, j.walk_verdict};
 }
 
 // A lane-walked batch's descriptor, read by the walking lane itself: the
-// payload, its record count and index slots.  Returns false when the batch
-// is not lane-walked (incomplete, compressed or > kLaneWalkMax records).
+// payload, its record count (k_emit's WalkDesc) and its index slots, all
+// contiguous across the lanes of a wave; no batch result is touched (a
+// lane-strided 128-byte struct: two more lines per batch for 16 bytes).
+// Returns false when the batch is not lane-walked (incomplete, compressed or
+// > kLaneWalkMax records).
 DEV bool lane_walk_setup(const WalkCtx& j, uint64_t b, LaneWalk& w, bool& idx_ok) {
-    const rpgpu_batch_result* R = &j.batches[b];
-    const int32_t rc = R->record_count;
-    if (!lane_walked(R->flags, (uint32_t)R->attrs & 7u, rc)) return false;
-    const uint64_t S = j.seg_off[R->segment] + R->file_pos + RPGPU_HEADER_SIZE;
-    const uint32_t n = (uint32_t)(R->size_bytes - (int32_t)RPGPU_HEADER_SIZE);
+    const WalkDesc d = j.desc[b];
+    if (d.rc == kNotLaneWalked) return false;
     const uint64_t ib = j.slots[b], islots = j.slots[b + 1] - ib;
     idx_ok = ib + islots <= j.record_capacity;
-    lane_walk_begin(w, j.data + S, n, rc, (uint32_t)b, idx_ok ? j.records + ib : nullptr,
+    lane_walk_begin(w, j.data + d.start, d.n, d.rc, (uint32_t)b, idx_ok ? j.records + ib : nullptr,
                     idx_ok ? (uint32_t)islots : 0u);
     return true;
 }
 
-// A lane walk's verdict bits into the batch result (model/record.h:616-627
-// sync, :680-697 async).  flags is OR-ed: the CRC wave may be writing its
-// own bits into the same word at the same time.
+// A lane walk's verdict (model/record.h:616-627 sync, :680-697 async): the
+// bits, records_parsed and parse_err as ONE 8-byte store into the dense
+// verdict array; k_finalize_bitmap, which loads every batch's flags anyway,
+// merges it into the batch result.  (Written into the batch result from
+// here it was an atomic and two partial stores into a line of its own per
+// batch: ~5 write requests and the read halves of the read-modify-writes.)
 DEV void lane_walk_finish(const WalkCtx& j, uint64_t b, const WalkResult& w, bool idx_ok, bool wire) {
-    rpgpu_batch_result* R = &j.batches[b];
     uint32_t f = RPGPU_F_PARSED, perr = w.err;
     if (perr == 0) {
         f |= RPGPU_F_PARSE_ASYNC_OK;
@@ -1205,10 +1202,8 @@ DEV void lane_walk_finish(const WalkCtx& j, uint64_t b, const WalkResult& w, boo
     }
     // wire: a failed sync record parse is the first batch do_load_slice
     // rejects (kafka/protocol/batch_reader.cc:129-151)
-    if (wire && !(f & RPGPU_F_PARSE_OK)) note_bad_lane(j, R->segment, b);
-    atomicOr(&R->flags, f);
-    R->records_parsed = w.parsed;
-    R->parse_err = (uint8_t)perr;
+    if (wire && !(f & RPGPU_F_PARSE_OK)) note_bad_lane(j, j.batches[b].segment, b);
+    j.verdict[b] = walk_verdict_pack(f, w.parsed, perr);
 }
 
 __global__ __launch_bounds__(1024) void k_validate(DeviceJob j) {
@@ -1638,7 +1633,9 @@ __global__ __launch_bounds__(1024) void k_validate_decoded(DeviceJob j) {
 //   head  -> its region arrived: walk from the next turn
 //   walk  -> fetch C_k, parse record k, commit it
 // Batches with more records are walked by the wave-parallel walk inside
-// k_validate.
+// k_validate.  Every batch below the capacity gets its word of the verdict
+// array here, walked or not (0), so the array needs no clearing and
+// k_finalize_bitmap can merge it without looking at anything else.
 __global__ __launch_bounds__(256) void k_walk(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     enum : uint32_t { kIdle = 0, kHead = 1, kWalk = 2, kFin = 3 };
@@ -1666,6 +1663,8 @@ __global__ __launch_bounds__(256) void k_walk(DeviceJob j) {
                     wr.parsed = 0; wr.err = 0; wr.trailing = w.n;
                     lane_walk_finish(c, b, wr, idx_ok, wire);
                 } else st = kHead;
+            } else {
+                c.verdict[b] = 0;  // not walked: the merge leaves this batch's result alone
             }
         }
         uint32_t want = 0, rows = 0;

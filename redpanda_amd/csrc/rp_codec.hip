@@ -33,10 +33,36 @@
 #include "rp_device.h"
 // RPGPU_DSTAMPS: diagnostic build of the decode kernel (scripts/build_exp.py
 // dstamps -DRPGPU_DSTAMPS --unit rp_codec.hip): per unit kind, wall-clock
-// totals / maxima / finish times, printed by k_print_dstamps; never measured
+// totals / maxima / finish times, printed by k_print_dstamps; never measured.
+// DS(...) holds stamp statements inside a function; whole definitions stay
+// under a plain #ifdef.  g_dst's slots are named by DsSlot.
 #ifdef RPGPU_DSTAMPS
 #include <cstdio>
-__device__ unsigned long long g_dst[64];
+#define DS(...) __VA_ARGS__
+enum DsSlot {
+    // k_lz_exec's pieces by kind: wall-clock sum, then count (kind + 1)
+    kDsLz4 = 2, kDsRaw = 4, kDsSnappy = 6,
+    kDsLinkedN = 9, kDsLinkedClk = 10,  // linked frames
+    kDsRecords = 11, kDsPoolCut = 12,
+    // xbatch, through XRing::ds (ds_flush)
+    kDsScanClk = 16, kDsLitClk = 17, kDsRoundsClk = 18, kDsFlushClk = 19, kDsBatches = 20, kDsRounds = 21,
+    // k_lz_walk: long pieces, then lane pieces (sum, count, maximum and what took it), first and last wave end
+    kDsLongClk = 24, kDsLongN = 25, kDsLongMax = 26,
+    kDsLaneClk = 27, kDsLaneN = 28, kDsLaneMax = 29, kDsLaneMaxNrec = 30, kDsLaneMaxItem = 31,
+    kDsLongMaxNrec = 32, kDsLongMaxCsize = 33,
+    kDsEndMax = 34, kDsEndMin = 35,
+    // the snappy long walk
+    kDsSnapIters = 40, kDsSnapHops = 41, kDsSnapDecodeClk = 42, kDsSnapHopsClk = 43, kDsSnapRestClk = 44,
+    // [kDsBeforeInit, kDsSlots): k_lzf_walk / k_lzf_tail, which run before k_init_dstamps (it leaves them)
+    kDsBeforeInit = 46,
+    kDsLzfRounds = 48, kDsLzfSteps = 49, kDsLzfTails = 50, kDsLzfTailRecs = 51,
+    // xbatch's far sources, through XRing::ds
+    kDsFarBatches = 52, kDsFarLanes = 53, kDsFarDrains = 54, kDsMatchLanes = 55, kDsFarRoundsClk = 56,
+    kDsSlots = 64
+};
+__device__ unsigned long long g_dst[kDsSlots];
+#else
+#define DS(...)
 #endif
 
 namespace rp {
@@ -924,32 +950,21 @@ DEV int in_varint(In& in, int64_t pos, int64_t n, uint32_t& v) {
 }
 
 
-#ifndef RPGPU_LONG_LZ4
-#define RPGPU_LONG_LZ4 65536u
-#endif
-// dense pieces (decoded capacity >= RPGPU_DENSE_X10 / 10 x compressed, at least
-// RPGPU_DENSE_MIN compressed: thousands of short sequences) are wave-walked
+constexpr uint32_t kLongLz4 = 65536;  // compressed bytes above which a piece counts as long
+// dense pieces (decoded capacity >= kDenseX10 / 10 x compressed, at least
+// kDenseMin compressed: thousands of short sequences) are wave-walked
 // too, where the window-parallel parse takes ~13 sequences per step;
 // literal-heavy ones stay on the lane walk, whose 256-byte windows skip long
 // literals.  Measured (step ms C2 / C5): off 65.4 / 38.4; x3 from 4 KiB
 // 65.4 / 23.1; x2 from 1 KiB 64.5 / 23.1.
-#ifndef RPGPU_DENSE_X10
-#define RPGPU_DENSE_X10 20u
-#endif
-#ifndef RPGPU_DENSE_MIN
-#define RPGPU_DENSE_MIN 1024u
-#endif
-#ifndef RPGPU_ALONE_MIN
-#define RPGPU_ALONE_MIN 0u
-#endif
+constexpr uint32_t kDenseX10 = 20;
+constexpr uint32_t kDenseMin = 1024;
 DEV bool piece_dense(uint32_t csize, uint32_t cap) {
-    return RPGPU_DENSE_X10 && csize >= RPGPU_DENSE_MIN && 10ull * cap >= (uint64_t)RPGPU_DENSE_X10 * csize;
+    return csize >= kDenseMin && 10ull * cap >= (uint64_t)kDenseX10 * csize;
 }
-// the pieces k_lz_exec runs alone (the long list): long, dense, and (with
-// RPGPU_ALONE_MIN) every compressed piece of at least that many bytes
+// the pieces k_lz_exec runs alone (the long list): long and dense
 DEV bool piece_is_long(uint32_t kind, uint32_t csize, uint32_t cap) {
-    return !(kind & kBlkRaw) && ((kind & kBlkWhole) || csize > RPGPU_LONG_LZ4 || piece_dense(csize, cap) ||
-                                 (RPGPU_ALONE_MIN && csize >= RPGPU_ALONE_MIN));
+    return !(kind & kBlkRaw) && ((kind & kBlkWhole) || csize > kLongLz4 || piece_dense(csize, cap));
 }
 // Long pieces all run alone in k_lz_exec.  Dense ones are wave-walked only
 // when the job has few pieces for the lanes the walk keeps resident
@@ -957,13 +972,9 @@ DEV bool piece_is_long(uint32_t kind, uint32_t csize, uint32_t cap) {
 // ~250 K pieces: step 63.7 -> 56.2 ms with its dense LZ4 blocks on the lane
 // walk); with few, lanes sit idle behind the slowest ones (C5, ~55 K pieces:
 // 23.1 -> 31.5 ms without the wave walk, 28.9 with only its snappy chunks on
-// it).  RPGPU_DENSE_WALK 1 / 0 force it on / off (diagnostics).
-#ifndef RPGPU_DENSE_WALK
-#define RPGPU_DENSE_WALK 2
-#endif
+// it).
 DEV bool piece_wave_walked(uint32_t kind, uint32_t csize, uint32_t cap, bool few_pieces) {
-    const bool dense = RPGPU_DENSE_WALK == 1 || (RPGPU_DENSE_WALK == 2 && few_pieces);
-    return !(kind & kBlkRaw) && ((kind & kBlkWhole) || csize > RPGPU_LONG_LZ4 || (dense && piece_dense(csize, cap)));
+    return !(kind & kBlkRaw) && ((kind & kBlkWhole) || csize > kLongLz4 || (few_pieces && piece_dense(csize, cap)));
 }
 
 // long pieces base + i for the set bits i of m (lane 0): one atomic per 64
@@ -982,10 +993,7 @@ DEV void note_longs(const DeviceJob& j, uint32_t base, uint64_t m, uint64_t w) {
     }
 }
 // k_lzf_walk's per-lane window (design note at k_lzf_walk)
-#ifndef RPGPU_LZF_WIN
-#define RPGPU_LZF_WIN 256
-#endif
-constexpr uint32_t kFWin = RPGPU_LZF_WIN;  // sequence starts walked per staged window
+constexpr uint32_t kFWin = 256;            // sequence starts walked per staged window
 constexpr uint32_t kFSlot = kFWin + 32;    // + a 16-byte read at the last start, or the offset bytes after it
 constexpr uint32_t kFMarginIn = 64, kFMarginOut = 128;
 static_assert(kFWin % 32 == 0 && kFWin >= 64, "lane window");
@@ -1316,19 +1324,16 @@ __global__ __launch_bounds__(256) void k_decode(DeviceJob j) {
 // of LDS and load latencies per wave, and throughput scales with the waves
 // resident (16 KiB: 10 per CU; the 64 KiB ring of the first wave engine
 // allowed 2).  Matches reaching further back than the ring read the arena.
-#ifndef RPGPU_XRING_KIB
-#define RPGPU_XRING_KIB 16
-#endif
-constexpr uint32_t kXRing = RPGPU_XRING_KIB * 1024u, kXM = kXRing - 1;
+constexpr uint32_t kXRing = 16u * 1024u, kXM = kXRing - 1;
 static_assert((kXRing & kXM) == 0 && kXRing >= 16384, "ring: a power of two >= 16 KiB");
 // longer literals / matches run wave-cooperatively (a 64-record batch then
 // writes at most 128 kBig bytes)
-constexpr uint32_t kBig = kXRing >= 32768 ? 128 : 64;
+constexpr uint32_t kBig = 64;
 // ring stores are deferred: unflushed output stays below kFlushLag (+ the
 // 1 KiB flush granule + one batch), so most batches issue no global store
 // and the loads they wait on are counted exactly (gfx9's vmcnt also counts
 // stores)
-constexpr uint32_t kFlushLag = kXRing >= 65536 ? (24u << 10) : kXRing / 4;
+constexpr uint32_t kFlushLag = kXRing / 4;
 
 // a batch overwrites ring slots up to 128 kBig bytes behind the front, and
 // its far matches read up to kBig bytes past (front - ring): both must lie
@@ -1341,11 +1346,7 @@ static_assert(kXRing >= kFlushLag + 2048 + 128, "ring too small for xbig's far r
 // single copy) and the short-offset pattern selectors.  (One wave per
 // workgroup left no room for shared tables; 9 rings + 8.5 KiB fit 160 KiB,
 // as many waves per CU as the 10 one-wave workgroups that were resident.)
-#ifdef RPGPU_EXEC_WAVES
-constexpr uint32_t kExecWaves = RPGPU_EXEC_WAVES;  // (experiment builds)
-#else
 constexpr uint32_t kExecWaves = (160u * 1024u - 8704u) / kXRing;
-#endif
 constexpr uint32_t kXCrcOff = kExecWaves * kXRing;
 constexpr uint32_t kXPatOff = kXCrcOff + 8192u;
 constexpr uint32_t kXLds = kXPatOff + 512u;
@@ -1413,9 +1414,6 @@ DEV void crc_init(CrcState& c) {
 }
 // the next 1 KiB row of the output (this lane's 16 bytes; zero past the end)
 DEV void crc_row(CrcState& c, lds_cu32* ct, const uint4& v) {
-#if defined(RPGPU_XABL) && RPGPU_XABL == 3
-    return;  // ablation (diagnostic build only): no streaming CRC
-#endif
     if (c.hp) {
         xbraid(c, ct, 0, c.pend.x);
         xbraid(c, ct, 1, c.pend.y);
@@ -1529,21 +1527,14 @@ DEV uint32_t wave_scan(uint32_t v) {
 
 // one lane's match: ml bytes at d from d - off (every source byte final or
 // this match's own earlier output)
-// RPGPU_XMATCH_BATCH: 3 (default) = a source that does not overlap its
-// destination read 32 bytes at a time, both reads before the stores (C2
-// decode 24.4 -> 23.9 ms); 0 = 16 bytes at a time; experiment builds: 1 = a
-// non-overlapping match's source loaded whole before its stores (1632 VGPR
-// spills: C2 decode 26 -> 47 ms); 2 = far sources two 16-byte loads at a time
-#ifndef RPGPU_XMATCH_BATCH
-#define RPGPU_XMATCH_BATCH 3
-#endif
 DEV void xmatch(XRing& x, uint32_t d, uint32_t off, uint32_t ml, bool far) {
     const uint32_t s = d - off;
-#if RPGPU_XMATCH_BATCH == 3
     // a source that does not overlap the destination (off >= ml: C2 99.96 %
     // of matches; every far one) is read 32 bytes at a time, both loads in
     // flight before the stores: one LDS (or arena) latency per 32 bytes
-    // instead of one per 16 (the round's chain is these latencies)
+    // instead of one per 16 (the round's chain is these latencies): C2 decode
+    // 24.4 -> 23.9 ms.  (Loading the whole source before the stores spilled:
+    // 1632 VGPR spills, C2 decode 26 -> 47 ms.)
     if (far || off >= ml) {
         for (uint32_t c = 0; c < ml; c += 32) {
             uint4 v0, v1;
@@ -1558,50 +1549,6 @@ DEV void xmatch(XRing& x, uint32_t d, uint32_t off, uint32_t ml, bool far) {
             }
             xst(x.r, d + c, v0, ml - c < 16 ? ml - c : 16);
             if (c + 16 < ml) xst(x.r, d + c + 16, v1, ml - c - 16 < 16 ? ml - c - 16 : 16);
-        }
-        return;
-    }
-#endif
-#if RPGPU_XMATCH_BATCH == 2
-    if (far) {
-        for (uint32_t c = 0; c < ml; c += 32) {
-            const auto t0 = __builtin_amdgcn_raw_buffer_load_b128(x.rs, s + c, 0, kSc1);
-            const auto t1 = __builtin_amdgcn_raw_buffer_load_b128(x.rs, s + c + 16, 0, kSc1);
-            xst(x.r, d + c, make_uint4(t0[0], t0[1], t0[2], t0[3]), ml - c < 16 ? ml - c : 16);
-            if (c + 16 < ml) xst(x.r, d + c + 16, make_uint4(t1[0], t1[1], t1[2], t1[3]), ml - c - 16 < 16 ? ml - c - 16 : 16);
-        }
-        return;
-    }
-#endif
-#if RPGPU_XMATCH_BATCH == 1
-    // ml <= kBig here (xbatch).  A source that does not overlap the
-    // destination (every far one: off > ring - 1 KiB) is read whole before
-    // anything is stored: one load latency per match instead of one per 16
-    // bytes
-    if (far || off >= ml) {
-        uint4 t[kBig / 16];
-#pragma unroll
-        for (uint32_t k = 0; k < kBig / 16; k++) {
-            t[k] = make_uint4(0u, 0u, 0u, 0u);
-            if (16 * k < ml) {
-                if (far) {
-                    const auto v = __builtin_amdgcn_raw_buffer_load_b128(x.rs, s + 16 * k, 0, kSc1);
-                    t[k] = make_uint4(v[0], v[1], v[2], v[3]);
-                } else {
-                    t[k] = xld16(x.r, s + 16 * k);
-                }
-            }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kBig / 16; k++)
-            if (16 * k < ml) xst(x.r, d + 16 * k, t[k], ml - 16 * k < 16 ? ml - 16 * k : 16);
-        return;
-    }
-#endif
-    if (far) {
-        for (uint32_t c = 0; c < ml; c += 16) {
-            const auto t = __builtin_amdgcn_raw_buffer_load_b128(x.rs, s + c, 0, kSc1);
-            xst(x.r, d + c, make_uint4(t[0], t[1], t[2], t[3]), ml - c < 16 ? ml - c : 16);
         }
         return;
     }
@@ -1675,15 +1622,11 @@ DEV void lit_fix(Lit& L) {
 // literal bytes (loaded a window ahead)
 DEV void xbatch(XRing& x, const Src& s, const SeqRec& r, uint32_t lo, uint32_t hi_lane, const Lit& lit) {
     const uint32_t l = lane();
-#ifdef RPGPU_DSTAMPS
-    const uint64_t c0 = __builtin_amdgcn_s_memtime();
-#endif
+    DS(const uint64_t c0 = __builtin_amdgcn_s_memtime();)
     const bool v = l >= lo && l < hi_lane;
     const uint32_t len = v ? r.ll + r.ml : 0u;
     const uint32_t incl = wave_scan(len);
-#ifdef RPGPU_DSTAMPS
-    const uint64_t c1 = __builtin_amdgcn_s_memtime();
-#endif
+    DS(const uint64_t c1 = __builtin_amdgcn_s_memtime();)
     const uint32_t o = x.op + incl - len;
     const uint32_t hi = x.op + rl(incl, (int)hi_lane - 1);
     if (v && r.ll) {
@@ -1693,31 +1636,18 @@ DEV void xbatch(XRing& x, const Src& s, const SeqRec& r, uint32_t lo, uint32_t h
     }
     const uint32_t d = o + r.ll, src = d - r.off;
     bool pend = v && r.ml > 0;
-#ifdef RPGPU_DSTAMPS
-    const uint64_t c2 = __builtin_amdgcn_s_memtime();
-    uint32_t rounds = 0;
-#endif
+    DS(const uint64_t c2 = __builtin_amdgcn_s_memtime();)
+    DS(uint32_t rounds = 0;)
     // sources before (batch end - 64 KiB): their ring slots may be rewritten by this batch
-#if defined(RPGPU_XABL) && RPGPU_XABL == 2
-    const bool far = false;  // ablation (diagnostic build only): far sources read the ring
-#else
     const bool far = x.linked && pend && hi > kXRing && src < hi - kXRing;
-#endif
-#if defined(RPGPU_XABL) && RPGPU_XABL == 1
-    pend = false;  // ablation (diagnostic build only): no match copies
-#endif
+    DS(const uint64_t farm = __ballot(far), mm = __ballot(pend);)
+    DS(x.ds[6] += farm ? 1u : 0u;)
+    DS(x.ds[7] += (uint64_t)__builtin_popcountll(farm);)
+    DS(x.ds[9] += (uint64_t)__builtin_popcountll(mm);)
     // a far source was stored by an earlier flush: wait only while a flush
     // may still be in flight (a wait drains every earlier memory op)
-#ifdef RPGPU_DSTAMPS
-    const uint64_t farm = __ballot(far), mm = __ballot(pend);
-    x.ds[6] += farm ? 1u : 0u;
-    x.ds[7] += (uint64_t)__builtin_popcountll(farm);
-    x.ds[9] += (uint64_t)__builtin_popcountll(mm);
-#endif
     if (__ballot(far && src + r.ml > x.safe) && x.fpend) {
-#ifdef RPGPU_DSTAMPS
-        if (l == 0) atomicAdd(&g_dst[54], 1ull);
-#endif
+        DS(if (l == 0) atomicAdd(&g_dst[kDsFarDrains], 1ull);)
         wait_vm();
         x.fpend = false;
         x.safe = x.flushed;
@@ -1725,41 +1655,32 @@ DEV void xbatch(XRing& x, const Src& s, const SeqRec& r, uint32_t lo, uint32_t h
     for (;;) {
         const uint64_t pm = __ballot(pend);
         if (!pm) break;
-#ifdef RPGPU_DSTAMPS
-        rounds++;
-#endif
+        DS(rounds++;)
         const int first = __builtin_ctzll(pm);
         const uint32_t f = rl(d, first);
-#if defined(RPGPU_XABL) && RPGPU_XABL == 4
-        const bool ready = pend;  // ablation (diagnostic build only): every match in one round, no dependencies
-#else
         const bool ready = pend && (src + r.ml <= f || l == (uint32_t)first);
-#endif
         if (ready) xmatch(x, d, r.off, r.ml, far);
         pend = pend && !ready;
     }
-#ifdef RPGPU_DSTAMPS
-    const uint64_t c3 = __builtin_amdgcn_s_memtime();
-#endif
+    DS(const uint64_t c3 = __builtin_amdgcn_s_memtime();)
     x.op = hi;
-#ifdef RPGPU_DSTAMPS
-    const uint64_t c4 = __builtin_amdgcn_s_memtime();
+    DS(const uint64_t c4 = __builtin_amdgcn_s_memtime();)
     // accumulated per piece, added to g_dst once per piece (ds_flush): an
     // atomic per batch from every wave perturbed the kernel it measured
-    x.ds[0] += c1 - c0;  // scan (waits for the batch's records / literals)
-    x.ds[1] += c2 - c1;  // literals
-    x.ds[2] += c3 - c2;  // rounds
-    x.ds[3] += c4 - c3;  // flush
-    x.ds[4] += 1u;       // batches
-    x.ds[5] += rounds;
-    x.ds[8] += farm ? c3 - c2 : 0u;  // rounds of batches with far lanes
-#endif
+    DS(x.ds[0] += c1 - c0;)  // scan (waits for the batch's records / literals)
+    DS(x.ds[1] += c2 - c1;)  // literals
+    DS(x.ds[2] += c3 - c2;)  // rounds
+    DS(x.ds[3] += c4 - c3;)  // flush
+    DS(x.ds[4] += 1u;)       // batches
+    DS(x.ds[5] += rounds;)
+    DS(x.ds[8] += farm ? c3 - c2 : 0u;)  // rounds of batches with far lanes
 }
 
 #ifdef RPGPU_DSTAMPS
 DEV void ds_flush(const XRing& x) {
     if (lane() != 0) return;
-    const int slot[10] = {16, 17, 18, 19, 20, 21, 52, 53, 56, 55};
+    const int slot[10] = {kDsScanClk, kDsLitClk, kDsRoundsClk, kDsFlushClk, kDsBatches,
+                          kDsRounds, kDsFarBatches, kDsFarLanes, kDsFarRoundsClk, kDsMatchLanes};
     for (int i = 0; i < 10; i++) atomicAdd(&g_dst[slot[i]], (unsigned long long)x.ds[i]);
 }
 #endif
@@ -1839,9 +1760,6 @@ struct FRecs {  // k_lzf_walk's 8-byte records {lip | ll << 16, ml | off << 16}
 // flush is issued at its top, before its prefetch loads: the waits the
 // register rotation needs at the window's end then find the stores and the
 // loads a window old.
-#ifndef RPGPU_XSPLIT
-#define RPGPU_XSPLIT 1
-#endif
 template <class RS>
 DEV void xwindows(XRing& x, const Src& s, const RS& rs, uint32_t cnt) {
     if (cnt == 0) return;
@@ -1864,7 +1782,7 @@ DEV void xwindows(XRing& x, const Src& s, const RS& rs, uint32_t cnt) {
         lit_fix(lit0);
         const uint32_t nb = cnt - b < 64 ? cnt - b : 64;
         const uint64_t bigm = __ballot(l < nb && (r0.ll > kBig || r0.ml > kBig));
-        if (RPGPU_XSPLIT && !bigm) {
+        if (!bigm) {
             xbatch(x, s, r0, 0, nb, lit0);
         } else {
             uint32_t lo = 0;
@@ -2032,9 +1950,6 @@ struct SlabSink {
 // block checksum, then the walk.  High occupancy: the lane walk is a chain
 // of dependent loads per lane.
 // ---------------------------------------------------------------------------
-#ifndef RPGPU_WALK_PRIO
-#define RPGPU_WALK_PRIO 0  // s_setprio of a wave walking a long piece (experiment builds)
-#endif
 constexpr uint32_t kWalkWin = 4096;  // staged stream bytes per wave (long pieces)
 
 
@@ -2112,16 +2027,12 @@ DEV void walk_snappy_long(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8*
     int64_t w0 = -1;
     lds_cu32* w32 = (lds_cu32*)win;
     const uint64_t below = (1ull << l) - 1;
-#ifdef RPGPU_DSTAMPS
-    uint64_t ds_it = 0, ds_hops = 0, ds_c0 = 0, ds_c1 = 0, ds_c2 = 0;
-#endif
+    DS(uint64_t ds_it = 0, ds_hops = 0, ds_c0 = 0, ds_c1 = 0, ds_c2 = 0;)
     while (st == 0 && !cut) {
         ip = uni32(ip);
         op = uni64(op);
-#ifdef RPGPU_DSTAMPS
-        const uint64_t q0 = __builtin_amdgcn_s_memtime();
-        ds_it++;
-#endif
+        DS(const uint64_t q0 = __builtin_amdgcn_s_memtime();)
+        DS(ds_it++;)
         if (ip >= n) {
             st = op == ulen ? 1 : -1;
             break;
@@ -2139,9 +2050,7 @@ DEV void walk_snappy_long(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8*
         const uint32_t ib = ip + 64;
         const SnapCand a = snappy_cand(w32, w0, ip + l, n);
         const SnapCand b = snappy_cand(w32, w0, ib + l, n);
-#ifdef RPGPU_DSTAMPS
-        const uint64_t q1 = __builtin_amdgcn_s_memtime();
-#endif
+        DS(const uint64_t q1 = __builtin_amdgcn_s_memtime();)
         // the true tags of each half by pointer doubling: J = the lane of the
         // next tag in the half (itself where the chain leaves the half, ends
         // the stream or meets a bad tag), F = the lanes visited from here;
@@ -2173,12 +2082,10 @@ DEV void walk_snappy_long(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8*
         if (qa < n && e < 64u)
             cb = (uint64_t)uni32(rl((uint32_t)Fb, (int)e)) | ((uint64_t)uni32(rl((uint32_t)(Fb >> 32), (int)e)) << 32);
         const uint32_t qn = cb ? uni32(rl(b.nxt, 63 - __builtin_clzll(cb))) : qa;
-#ifdef RPGPU_DSTAMPS
-        ds_hops += (uint64_t)(__builtin_popcountll(ca) + __builtin_popcountll(cb));
-        const uint64_t q2 = __builtin_amdgcn_s_memtime();
-        ds_c0 += q1 - q0;
-        ds_c1 += q2 - q1;
-#endif
+        DS(ds_hops += (uint64_t)(__builtin_popcountll(ca) + __builtin_popcountll(cb));)
+        DS(const uint64_t q2 = __builtin_amdgcn_s_memtime();)
+        DS(ds_c0 += q1 - q0;)
+        DS(ds_c1 += q2 - q1;)
         const bool ona = (ca >> l) & 1, onb = (cb >> l) & 1;
         // output before each chain tag: 32-bit DPP scans (a good chain tag's
         // output is a literal inside the stream or a copy of <= 64 bytes)
@@ -2241,19 +2148,15 @@ DEV void walk_snappy_long(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8*
         }
         op += ta + rl(ibn, 63);
         ip = qn;
-#ifdef RPGPU_DSTAMPS
-        ds_c2 += __builtin_amdgcn_s_memtime() - q2;
-#endif
+        DS(ds_c2 += __builtin_amdgcn_s_memtime() - q2;)
     }
-#ifdef RPGPU_DSTAMPS
-    if (lane() == 0) {
-        atomicAdd(&g_dst[40], ds_it);
-        atomicAdd(&g_dst[41], ds_hops);
-        atomicAdd(&g_dst[42], ds_c0);
-        atomicAdd(&g_dst[43], ds_c1);
-        atomicAdd(&g_dst[44], ds_c2);
-    }
-#endif
+    DS(if (lane() == 0) {
+        atomicAdd(&g_dst[kDsSnapIters], ds_it);
+        atomicAdd(&g_dst[kDsSnapHops], ds_hops);
+        atomicAdd(&g_dst[kDsSnapDecodeClk], ds_c0);
+        atomicAdd(&g_dst[kDsSnapHopsClk], ds_c1);
+        atomicAdd(&g_dst[kDsSnapRestClk], ds_c2);
+    })
     pc.ps.ip = (int32_t)ip;
     pc.ps.op = (int32_t)(uint32_t)op;
     pc.ps.st = st;
@@ -2451,9 +2354,7 @@ DEV void walk_lz4_wave(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8* wi
 
 DEV void walk_long(const DeviceJob& j, uint32_t p, lds_u8* win) {
     const uint32_t l = lane();
-#ifdef RPGPU_DSTAMPS
-    const uint64_t t0 = wall_clock64();
-#endif
+    DS(const uint64_t t0 = wall_clock64();)
     BlockItem it;
     it.src = uni64(j.blocks[p].src);
     it.dst = 0;
@@ -2516,12 +2417,10 @@ DEV void walk_long(const DeviceJob& j, uint32_t p, lds_u8* win) {
         out.ulen = pc.ps.ulen;
         out.safe = pc.ps.safe;
         j.pstate[p] = out;
-#ifdef RPGPU_DSTAMPS
-        const uint64_t dt = wall_clock64() - t0;
-        atomicAdd(&g_dst[24], dt);
-        atomicAdd(&g_dst[25], 1ull);
-        if (dt > atomicMax(&g_dst[26], dt)) { g_dst[32] = out.nrec; g_dst[33] = it.csize; }
-#endif
+        DS(const uint64_t dt = wall_clock64() - t0;)
+        DS(atomicAdd(&g_dst[kDsLongClk], dt);)
+        DS(atomicAdd(&g_dst[kDsLongN], 1ull);)
+        DS(if (dt > atomicMax(&g_dst[kDsLongMax], dt)) { g_dst[kDsLongMaxNrec] = out.nrec; g_dst[kDsLongMaxCsize] = it.csize; })
     }
 }
 
@@ -2548,10 +2447,7 @@ DEV void put_pstate(const DeviceJob& j, uint32_t p, const PState& ps, uint32_t n
 // needed a new window), ~4 us per sequence on C2's JSON blocks.  Window
 // size measured (C2 / C5 decode ms): 64 B 47.7 / 45.6, 192 B 44.4 / 43.9,
 // 256 B 43.4 / 40.4, 512 B 46.6 / 35.8 (fewer resident waves).
-#ifndef RPGPU_LANE_WIN
-#define RPGPU_LANE_WIN 256
-#endif
-constexpr uint32_t kLaneWin = RPGPU_LANE_WIN, kLaneSlot = kLaneWin + 16;  // + the spare bytes ld16's window reads need
+constexpr uint32_t kLaneWin = 256, kLaneSlot = kLaneWin + 16;  // + the spare bytes ld16's window reads need
 
 __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
     constexpr uint32_t kWaveLds = 64 * kLaneSlot > kWalkWin + 16 ? 64 * kLaneSlot : kWalkWin + 16;
@@ -2571,13 +2467,7 @@ __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
         if (uni32(j.blocks[p].fast) != kLzfNone) continue;  // the fast path has it
         if (!piece_wave_walked(uni32(j.blocks[p].kind), uni32(j.blocks[p].csize), uni32(j.blocks[p].cap), few))
             continue;  // a dense piece: the lane walk takes it
-#if RPGPU_WALK_PRIO
-        __builtin_amdgcn_s_setprio(RPGPU_WALK_PRIO);
-#endif
         walk_long(j, p, wl);
-#if RPGPU_WALK_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     }
     lds_u8* slot = wl + kLaneSlot * lane();
     bool active = false, drained = false;
@@ -2733,9 +2623,7 @@ DEV void xring_init(XRing& x, const DeviceJob& j, lds_u8* ring, uint64_t dst, bo
     x.safe = 0;
     const uint64_t room = j.decoded_capacity - dst;
     x.rs = __builtin_amdgcn_make_buffer_rsrc(x.dst, 0, (int)(room < 0x7FFFFFFFull ? room : 0x7FFFFFFFull), kBufFlags);
-#ifdef RPGPU_DSTAMPS
-    for (int i = 0; i < 10; i++) x.ds[i] = 0;
-#endif
+    DS(for (int i = 0; i < 10; i++) x.ds[i] = 0;)
 }
 
 // the blocks of one linked LZ4F frame, in order, one position space
@@ -2745,9 +2633,7 @@ DEV void exec_linked(const DeviceJob& j, lds_u8* ring, SeqRec* buf, uint32_t ite
     const uint64_t fdst = uni64(j.dcap[uni32(j.decode_list[item])]);
     XRing x;
     xring_init(x, j, ring, fdst, true, true, pat, ct);
-#ifdef RPGPU_DSTAMPS
-    const uint64_t t1 = wall_clock64();
-#endif
+    DS(const uint64_t t1 = wall_clock64();)
     bool ok = true;
     for (uint32_t k = 0; k < nb; k++) {
         const uint32_t at = x.op;
@@ -2762,10 +2648,8 @@ DEV void exec_linked(const DeviceJob& j, lds_u8* ring, SeqRec* buf, uint32_t ite
     // the frame's whole output, one stream (its blocks are contiguous)
     const uint32_t fcrc = ok ? crc_finish(x, j.tables, x.op) : 0u;
     if (lane() == 0) j.blocks[first].crc = fcrc;
-#ifdef RPGPU_DSTAMPS
-    if (lane() == 0) { atomicAdd(&g_dst[10], wall_clock64() - t1); atomicAdd(&g_dst[9], 1ull); }
-    ds_flush(x);
-#endif
+    DS(if (lane() == 0) { atomicAdd(&g_dst[kDsLinkedClk], wall_clock64() - t1); atomicAdd(&g_dst[kDsLinkedN], 1ull); })
+    DS(ds_flush(x);)
 }
 
 // one independent piece
@@ -2782,9 +2666,7 @@ DEV void exec_one(const DeviceJob& j, lds_u8* ring, SeqRec* buf, uint32_t p, uin
         XRing x;
         // a piece longer than the ring wraps it: wrap-aware like a linked frame
         xring_init(x, j, ring, dst, uni32(j.blocks[p].cap) > kXRing, false, pat, ct);
-#ifdef RPGPU_DSTAMPS
-        const uint64_t e0 = wall_clock64();
-#endif
+        DS(const uint64_t e0 = wall_clock64();)
         const int32_t dd = exec_piece(x, j, p, 0, buf);
         if (dd >= 0) xflush(x, x.op);
         const uint32_t pcrc = dd >= 0 ? crc_finish(x, j.tables, x.op) : 0u;
@@ -2792,16 +2674,14 @@ DEV void exec_one(const DeviceJob& j, lds_u8* ring, SeqRec* buf, uint32_t p, uin
             j.blocks[p].out = dd;
             j.blocks[p].crc = pcrc;
         }
-#ifdef RPGPU_DSTAMPS
-        if (lane() == 0) {
-            const int k = (kind & kBlkRaw) ? 4 : (kind & kBlkSnappy) ? 6 : 2;
+        DS(if (lane() == 0) {
+            const int k = (kind & kBlkRaw) ? kDsRaw : (kind & kBlkSnappy) ? kDsSnappy : kDsLz4;
             atomicAdd(&g_dst[k], wall_clock64() - e0);
             atomicAdd(&g_dst[k + 1], 1ull);
-            atomicAdd(&g_dst[11], (unsigned long long)j.pstate[p].nrec);
-            if (j.pstate[p].st == 0) atomicAdd(&g_dst[12], 1ull);
-        }
-        ds_flush(x);
-#endif
+            atomicAdd(&g_dst[kDsRecords], (unsigned long long)j.pstate[p].nrec);
+            if (j.pstate[p].st == 0) atomicAdd(&g_dst[kDsPoolCut], 1ull);
+        })
+        DS(ds_flush(x);)
     }
 }
 
@@ -2871,10 +2751,8 @@ __global__ __launch_bounds__(64 * kExecWaves) void k_lz_exec(DeviceJob j) {
 // the copy's HBM traffic hides behind the parse instead of holding k_lz_exec's
 // ring waves through 16 dependent load rounds per block.
 // ---------------------------------------------------------------------------
-#ifndef RPGPU_RAW_THREADS
-#define RPGPU_RAW_THREADS 1024
-#endif
-__global__ __launch_bounds__(RPGPU_RAW_THREADS) void k_raw_copy(DeviceJob j) {
+constexpr uint32_t kRawThreads = 1024;
+__global__ __launch_bounds__(kRawThreads) void k_raw_copy(DeviceJob j) {
     __shared__ uint32_t ct_w[2048];
     for (uint32_t i = threadIdx.x; i < 1024u; i += blockDim.x) {
         ct_w[i] = j.tables->braid[i >> 8][i & 255u];
@@ -3092,9 +2970,7 @@ __global__ __launch_bounds__(256) void k_decode_finish(DeviceJob j, int defer) {
 // k_content_apply applies it after the join.  Four waves per workgroup, one
 // per SIMD: with one-wave workgroups two hashing waves could share a SIMD,
 // each at half speed (the longest hash 2.0 -> 2.95 ms).
-#ifndef RPGPU_XXH_PRIO
-#define RPGPU_XXH_PRIO 1
-#endif
+constexpr int kXxhPrio = 1;
 __global__ __launch_bounds__(256) void k_content_xxh(DeviceJob j) {
     __shared__ __attribute__((aligned(16))) uint8_t xb[4][1024];
     lds_u8* xbuf = (lds_u8*)xb[threadIdx.x >> 6];
@@ -3103,7 +2979,7 @@ __global__ __launch_bounds__(256) void k_content_xxh(DeviceJob j) {
     // first in issue on a shared SIMD (k_dchain, which waits on memory, is
     // above it): beside k_decode_finish's waves at equal priority the chains
     // ran ~1.4x their time alone
-    __builtin_amdgcn_s_setprio(RPGPU_XXH_PRIO);
+    __builtin_amdgcn_s_setprio(kXxhPrio);
     for (;;) {
         const uint32_t item = wave_fetch_add(&j.counters[44], 1u);
         if (item >= count) break;
@@ -3175,26 +3051,32 @@ __global__ void k_print_dstamps() {
     const unsigned long long* g = g_dst;
     printf("RPGPU_DSTAMPS lz4 pieces=%llu exec_ms=%.1f | raw=%llu exec_ms=%.1f | snappy=%llu exec_ms=%.1f | "
            "linked=%llu exec_ms=%.1f | records=%llu pool-cut=%llu (wave-summed ms)\n",
-           g[3], g[2] / 1e5, g[5], g[4] / 1e5, g[7], g[6] / 1e5, g[9], g[10] / 1e5, g[11], g[12]);
-    printf("RPGPU_DSTAMPS batches=%llu rounds=%llu | per batch clk: scan=%.0f lit=%.0f rounds=%.0f flush=%.0f\n", g[20], g[21],
-           (double)g[16] / g[20], (double)g[17] / g[20], (double)g[18] / g[20], (double)g[19] / g[20]);
+           g[kDsLz4 + 1], g[kDsLz4] / 1e5, g[kDsRaw + 1], g[kDsRaw] / 1e5, g[kDsSnappy + 1], g[kDsSnappy] / 1e5,
+           g[kDsLinkedN], g[kDsLinkedClk] / 1e5, g[kDsRecords], g[kDsPoolCut]);
+    printf("RPGPU_DSTAMPS batches=%llu rounds=%llu | per batch clk: scan=%.0f lit=%.0f rounds=%.0f flush=%.0f\n",
+           g[kDsBatches], g[kDsRounds], (double)g[kDsScanClk] / g[kDsBatches], (double)g[kDsLitClk] / g[kDsBatches],
+           (double)g[kDsRoundsClk] / g[kDsBatches], (double)g[kDsFlushClk] / g[kDsBatches]);
     printf("RPGPU_DSTAMPS walk long=%llu sum_ms=%.1f max_ms=%.2f (nrec %llu csize %llu) | lane pieces=%llu sum_ms=%.1f "
            "max_ms=%.2f (nrec %llu csize %llu kind %llu) | wave end spread ms=%.2f\n",
-           g[25], g[24] / 1e5, g[26] / 1e5, g[32], g[33], g[28], g[27] / 1e5, g[29] / 1e5, g[30], g[31] & 0xFFFFFFFFull,
-           g[31] >> 32, (double)(g[34] - g[35]) / 1e5);
+           g[kDsLongN], g[kDsLongClk] / 1e5, g[kDsLongMax] / 1e5, g[kDsLongMaxNrec], g[kDsLongMaxCsize], g[kDsLaneN],
+           g[kDsLaneClk] / 1e5, g[kDsLaneMax] / 1e5, g[kDsLaneMaxNrec], g[kDsLaneMaxItem] & 0xFFFFFFFFull,
+           g[kDsLaneMaxItem] >> 32, (double)(g[kDsEndMax] - g[kDsEndMin]) / 1e5);
     printf("RPGPU_DSTAMPS snappy-long iterations=%llu hops=%llu | per iteration clk: decode=%.0f hops=%.0f rest=%.0f\n",
-           g[40], g[41], (double)g[42] / (g[40] ? g[40] : 1), (double)g[43] / (g[40] ? g[40] : 1),
-           (double)g[44] / (g[40] ? g[40] : 1));
-    printf("RPGPU_DSTAMPS lzf walk rounds=%llu wave-steps=%llu | tails=%llu tail records=%llu\n", g[48], g[49], g[50],
-           g[51]);
+           g[kDsSnapIters], g[kDsSnapHops], (double)g[kDsSnapDecodeClk] / (g[kDsSnapIters] ? g[kDsSnapIters] : 1),
+           (double)g[kDsSnapHopsClk] / (g[kDsSnapIters] ? g[kDsSnapIters] : 1),
+           (double)g[kDsSnapRestClk] / (g[kDsSnapIters] ? g[kDsSnapIters] : 1));
+    printf("RPGPU_DSTAMPS lzf walk rounds=%llu wave-steps=%llu | tails=%llu tail records=%llu\n", g[kDsLzfRounds],
+           g[kDsLzfSteps], g[kDsLzfTails], g[kDsLzfTailRecs]);
     printf("RPGPU_DSTAMPS exec batches with far lanes=%llu far lanes=%llu far drains=%llu match lanes=%llu | rounds clk "
-           "in batches with far lanes=%.0f per batch (all batches %.0f)\n", g[52], g[53], g[54], g[55],
-           (double)g[56] / (g[52] ? g[52] : 1), (double)g[18] / (g[20] ? g[20] : 1));
-    for (int i = 0; i < 64; i++) g_dst[i] = 0;
+           "in batches with far lanes=%.0f per batch (all batches %.0f)\n",
+           g[kDsFarBatches], g[kDsFarLanes], g[kDsFarDrains], g[kDsMatchLanes],
+           (double)g[kDsFarRoundsClk] / (g[kDsFarBatches] ? g[kDsFarBatches] : 1),
+           (double)g[kDsRoundsClk] / (g[kDsBatches] ? g[kDsBatches] : 1));
+    for (int i = 0; i < kDsSlots; i++) g_dst[i] = 0;
 }
 __global__ void k_init_dstamps() {
-    for (int i = 0; i < 46; i++) g_dst[i] = 0;  // [46, 64): k_lzf_walk / k_lzf_tail, which run before it
-    g_dst[35] = ~0ull;
+    for (int i = 0; i < kDsBeforeInit; i++) g_dst[i] = 0;  // the rest: k_lzf_walk / k_lzf_tail, which run before it
+    g_dst[kDsEndMin] = ~0ull;
 }
 #endif
 
@@ -3319,9 +3201,7 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
     int32_t need = 0;
     bool linked = false;
     Src s{nullptr, 0, 0};
-#ifdef RPGPU_DSTAMPS
-    uint64_t d_rounds = 0, d_steps = 0;
-#endif
+    DS(uint64_t d_rounds = 0, d_steps = 0;)
     for (;;) {
         // lanes without a block take the next ones: one claim per wave
         for (;;) {
@@ -3380,13 +3260,9 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
         // walk the window: 0 on, 1 the tail, 2 reject, 3 restage
         bool go = active;
         uint32_t outcome = 0;
-#ifdef RPGPU_DSTAMPS
-        d_rounds++;
-#endif
+        DS(d_rounds++;)
         while (__ballot(go)) {
-#ifdef RPGPU_DSTAMPS
-            d_steps++;
-#endif
+            DS(d_steps++;)
             uint32_t st;
             const FSeq q = fseq_w(slot, wb, go ? ip : wb, n, st);
             const uint32_t opl = op + q.ll, ope = opl + q.ml;
@@ -3427,12 +3303,10 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
             active = false;
         }
     }
-#ifdef RPGPU_DSTAMPS
-    if (lane() == 0) {
-        atomicAdd(&g_dst[48], d_rounds);
-        atomicAdd(&g_dst[49], d_steps);
-    }
-#endif
+    DS(if (lane() == 0) {
+        atomicAdd(&g_dst[kDsLzfRounds], d_rounds);
+        atomicAdd(&g_dst[kDsLzfSteps], d_steps);
+    })
 }
 
 // the tails k_lzf_walk filed: lz4_run from the first sequence that is not an
@@ -3456,10 +3330,8 @@ __global__ __launch_bounds__(256) void k_lzf_tail(DeviceJob j) {
         const uint32_t resv = (uint32_t)pst.ulen;
         FRecSink fs{j.frecs + pst.first_slab, pst.nrec, resv};
         lz4_run(s, (int32_t)it.cap, linked ? 65536 : 0, ps, fs);
-#ifdef RPGPU_DSTAMPS
-        atomicAdd(&g_dst[50], 1ull);
-        atomicAdd(&g_dst[51], (unsigned long long)(fs.n - pst.nrec));
-#endif
+        DS(atomicAdd(&g_dst[kDsLzfTails], 1ull);)
+        DS(atomicAdd(&g_dst[kDsLzfTailRecs], (unsigned long long)(fs.n - pst.nrec));)
         if (ps.st != 1) {
             j.blocks[p].out = -1;
             j.blocks[p].crc = 0u;
@@ -3508,7 +3380,7 @@ hipError_t launch_raw_copy(const DeviceJob& j, hipStream_t s, uint32_t cus) {
     if (!j.raw_list) return hipSuccess;
     // one 16-wave workgroup per CU (one 8 KiB CRC table copy: k_lzf_walk's
     // two 74 KiB workgroups per CU still fit beside it)
-    hipLaunchKernelGGL(k_raw_copy, dim3(cus), dim3(RPGPU_RAW_THREADS), 0, s, j);
+    hipLaunchKernelGGL(k_raw_copy, dim3(cus), dim3(kRawThreads), 0, s, j);
     return hipGetLastError();
 }
 

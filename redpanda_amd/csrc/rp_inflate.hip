@@ -41,7 +41,10 @@
         stmt;                                   \
         e.prof[k] += wall_clock64() - t0_;      \
     }
+#define ZS_ST(...) __VA_ARGS__  // stamp statements inside a function
 __device__ unsigned long long g_zst[16];  // [0..7] the wave decoder, [8..15] the lane parse
+#else
+#define ZS_ST(...)
 #endif
 #include "rp_zstd_core.h"
 
@@ -607,10 +610,6 @@ DEV int inflate_member(InfIn& in, InfTabs* T, InfOut& o, const InfSymTabs& ST, u
                     bb >>= len;
                     bc -= len;
                     if (sym < 256) {
-#ifdef RPGPU_GZ_NOOUT  // diagnostic variant: decode only (the check then fails), to time the symbol chain
-                        op++;
-                        continue;
-#endif
                         lb = l == nl ? sym : lb;
                         if (++nl == 64) spill();
                         continue;
@@ -645,10 +644,6 @@ DEV int inflate_member(InfIn& in, InfTabs* T, InfOut& o, const InfSymTabs& ST, u
                     bb >>= de;
                     bc -= de;
                     if (dist > op) return -1;  // invalid distance too far back
-#ifdef RPGPU_GZ_NOOUT
-                    op += ml;
-                    continue;
-#endif
                     inf_copy(o, op, dist, ml);
                     op += ml;
                     inf_flush_upto(o, op);
@@ -931,13 +926,8 @@ typedef __attribute__((address_space(3))) uint16_t gzs_lds_u16;
 // ring filled the CU, C6 resolve+plan 64.4 -> 60.3 ms); a match from farther
 // back reads the chunk's region in the pool (its flushed symbols) or, before
 // the chunk's start, is a placeholder
-#ifndef RPGPU_GZS_RING
-#define RPGPU_GZS_RING 4096
-#endif
-#ifndef RPGPU_GZS_WGS
-#define RPGPU_GZS_WGS 8  // k_gzsdecode workgroups (one wave) per CU
-#endif
-constexpr uint32_t kGzsRing = RPGPU_GZS_RING, kGzsMask = kGzsRing - 1;
+constexpr uint32_t kGzsRing = 4096, kGzsMask = kGzsRing - 1;
+constexpr uint32_t kGzsWgs = 8;  // k_gzsdecode workgroups (one wave) per CU
 static_assert((kGzsRing & kGzsMask) == 0 && kGzsRing >= 2048, "split-decode ring: a power of two >= 2 K symbols");
 constexpr uint32_t kGzsLds = 2 * kGzsRing + kInfTabBytes;
 
@@ -1629,9 +1619,7 @@ DEV ZDev zdev(const InfIn& in, uint8_t* lds, uint8_t* dst, uint64_t cap) {
     e.fstart = 0;
     e.lbuf = 0;
     e.nlit = 0;
-#ifdef RPGPU_ZSTAMPS
-    e.prof[0] = e.prof[1] = e.prof[2] = e.prof[3] = 0;
-#endif
+    ZS_ST(e.prof[0] = e.prof[1] = e.prof[2] = e.prof[3] = 0;)
     e.rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)(cap < 0x7FFFFFFFull ? cap : 0x7FFFFFFFull), kBufFlagsZs);
     return e;
 }
@@ -1727,11 +1715,7 @@ struct ZLane {
 #ifdef RPGPU_ZSTAMPS
     uint64_t prof[4];
 #endif
-#ifdef RPGPU_ZL_UNI  // (A/B: header bytes and table reads wave-uniform)
-    DEV uint32_t b(uint64_t i) { return uni32(i < n ? (uint32_t)src[i] : 0u); }
-#else
     DEV uint32_t b(uint64_t i) { return i < n ? (uint32_t)src[i] : 0u; }
-#endif
     DEV uint64_t le(uint64_t i, uint32_t k) {
         uint64_t v = 0;
         for (uint32_t t = 0; t < k; t++) v |= (uint64_t)b(i + t) << (8 * t);
@@ -1764,20 +1748,8 @@ struct ZLane {
     // (values stay in VGPRs: making the table reads wave-uniform, so that the
     // state moves to SGPRs and branches on SCC, measured 140 -> 159 ms per
     // 1 MiB member)
-#ifdef RPGPU_ZL_UNI
-    DEV uint32_t U(uint32_t x) { return uni32(x); }
-    DEV zs::SeqSym sym(const zs::SeqSym& t) {
-        uint64_t v;
-        __builtin_memcpy(&v, &t, 8);
-        v = uni64(v);
-        zs::SeqSym r;
-        __builtin_memcpy(&r, &v, 8);
-        return r;
-    }
-#else
     DEV uint32_t U(uint32_t x) { return x; }
     DEV zs::SeqSym sym(const zs::SeqSym& t) { return t; }
-#endif
     DEV void lit(uint32_t v) {
         if (nlit >= lcap) bad = true;
         else if (lane() == 0) lits[nlit] = (uint8_t)v;
@@ -1861,13 +1833,9 @@ struct ZLane {
     // lookups issued back to back (one LDS latency per four symbols); each
     // stream's last symbol (the X2 last-symbol rule) by zs::huf_one
     DEV void huf_all(zs::Tabs* T, zs::Lits& L, uint32_t hlog) {
-#ifdef RPGPU_ZSTAMPS
-        const uint64_t t0 = wall_clock64();
-#endif
+        ZS_ST(const uint64_t t0 = wall_clock64();)
         huf_all_(T, L, hlog);
-#ifdef RPGPU_ZSTAMPS
-        prof[2] += wall_clock64() - t0;
-#endif
+        ZS_ST(prof[2] += wall_clock64() - t0;)
     }
     // a block k_zlits decoded ahead: its bytes are in place; the streams are
     // set to the end states lits_finish then reads (ended exactly, or
@@ -2390,25 +2358,19 @@ DEV uint32_t zstd_fast_item(const DeviceJob& j, uint8_t* lds, uint32_t i, uint32
     e.bad = false;
     e.win = (inf_lds_u8*)lds;  // the ring's LDS (the wave decoder's, unused here)
     e.rr = 0;
-#ifdef RPGPU_ZSTAMPS
-    e.prof[0] = e.prof[1] = e.prof[2] = e.prof[3] = 0;
-#endif
+    ZS_ST(e.prof[0] = e.prof[1] = e.prof[2] = e.prof[3] = 0;)
     zs::Tabs* T = (zs::Tabs*)(lds + kInfRing);
     uint64_t total = 0;
     bool unsure = false;
-#ifdef RPGPU_ZSTAMPS
-    const uint64_t t0 = wall_clock64();
-#endif
+    ZS_ST(const uint64_t t0 = wall_clock64();)
     const int rc = zs::payload(e, T, n, total, unsure);
-#ifdef RPGPU_ZSTAMPS
-    if (lane() == 0) {
+    ZS_ST(if (lane() == 0) {
         for (int k = 0; k < 4; k++) atomicAdd(&g_zst[8 + k], (unsigned long long)e.prof[k]);
         atomicAdd(&g_zst[12], (unsigned long long)(wall_clock64() - t0));
         atomicAdd(&g_zst[13], 1ull);
         atomicAdd(&g_zst[14], (unsigned long long)(e.nrec + (e.nlit << 32)));
         atomicMax(&g_zst[15], (unsigned long long)(wall_clock64() - t0));
-    }
-#endif
+    })
     if (e.bad) return 0;  // (the header walk's sizes should always hold: the wave decoder then rules)
     if (rc != 0) {
         if (lane() == 0) {
@@ -2451,22 +2413,18 @@ DEV void zstd_first_item(const DeviceJob& j, uint8_t* lds, uint32_t i, uint32_t 
         const uint64_t cap = soff + guess <= j.inf_scratch_bytes ? guess : 0;
         ZDev e = zdev(in, lds, j.inf_scratch + soff, cap);
         bool unsure = false;
-#ifdef RPGPU_ZSTAMPS
-        const uint64_t t0 = wall_clock64();
-#endif
+        ZS_ST(const uint64_t t0 = wall_clock64();)
         rc = zs::payload(e, T, in.n, total, unsure);
         e.flush_all();
         again = unsure || e.stored < total;
         dirty = e.dirty;
-#ifdef RPGPU_ZSTAMPS
-        if (lane() == 0) {
+        ZS_ST(if (lane() == 0) {
             for (int k = 0; k < 4; k++) atomicAdd(&g_zst[k], (unsigned long long)e.prof[k]);
             atomicAdd(&g_zst[4], (unsigned long long)(wall_clock64() - t0));
             atomicAdd(&g_zst[5], 1ull);
             atomicAdd(&g_zst[6], (unsigned long long)total);
             atomicMax(&g_zst[7], (unsigned long long)(wall_clock64() - t0));
-        }
-#endif
+        })
     }
     const uint64_t cap = rc != 0 ? 0 : (total + 15) & ~15ull;
     if (lane() == 0) {
@@ -3610,7 +3568,7 @@ hipError_t launch_gzsplit(const DeviceJob& j, hipStream_t s, uint32_t grid, int 
     }
     if (part == 1) hipLaunchKernelGGL(k_gzsfind, dim3(grid * 5), dim3(64), kGzsFindLds, s, j);
     if (part == 2) {
-        hipLaunchKernelGGL(k_gzsdecode, dim3(grid * RPGPU_GZS_WGS), dim3(64), kGzsLds, s, j);
+        hipLaunchKernelGGL(k_gzsdecode, dim3(grid * kGzsWgs), dim3(64), kGzsLds, s, j);
         hipLaunchKernelGGL(k_gzsresolve, dim3(grid * 2), dim3(256), 0, s, j);
     }
     return hipGetLastError();

@@ -195,14 +195,8 @@ struct GzsItem {
     uint64_t guess;      // the member's output guess (sizes the region)
     uint32_t cap, pad;   // region symbols
 };
-#ifndef RPGPU_GZS_MIN  // (A/B variants: scripts/build_exp.py -DRPGPU_GZS_MIN=... / -DRPGPU_GZS_CHUNK=...)
-#define RPGPU_GZS_MIN 16384
-#endif
-#ifndef RPGPU_GZS_CHUNK
-#define RPGPU_GZS_CHUNK 16384
-#endif
-constexpr uint64_t kGzsMin = RPGPU_GZS_MIN;      // stored gzip payloads this large take the split decode
-constexpr uint64_t kGzsChunk = RPGPU_GZS_CHUNK;  // deflate bytes per chunk
+constexpr uint64_t kGzsMin = 16384;    // stored gzip payloads this large take the split decode
+constexpr uint64_t kGzsChunk = 16384;  // deflate bytes per chunk
 constexpr uint32_t kGzsMaxK = 256;     // chunks per member at most
 
 // job counters (DeviceJob::counters), zeroed per submit
@@ -210,12 +204,8 @@ constexpr size_t kCounterBytes = 256;
 
 // Stored payloads with at most kLaneWalkMax records are walked one lane per
 // batch by k_walk; k_validate walks the rest (and decoded payloads) with the
-// wave-parallel walk.  (k_emit and the validate kernels must agree on it: an
-// experiment build that changes it rebuilds rp_kernels.hip and rp_validate.hip.)
-#ifndef RPGPU_LANE_WALK_MAX
-#define RPGPU_LANE_WALK_MAX 256
-#endif
-constexpr int32_t kLaneWalkMax = RPGPU_LANE_WALK_MAX;
+// wave-parallel walk.  (k_emit and the validate kernels must agree on it.)
+constexpr int32_t kLaneWalkMax = 256;
 __host__ __device__ __forceinline__ bool lane_walked(uint32_t flags, uint32_t codec, int32_t rc) {
     return (flags & RPGPU_F_COMPLETE) && codec == 0 && rc <= kLaneWalkMax;
 }

@@ -294,11 +294,7 @@ struct Diag {
     uint64_t frec_cap = ~0ull;        // RPGPU_FREC_CAP=n: at most n fast-path records (listed groups mix with walked ones)
     size_t inf_pool = 0;              // RPGPU_INF_POOL_KIB=n: the gzip / zstd first-pass pool, at least 4 KiB (0: from the job)
     uint32_t zs_fast = 1;             // RPGPU_ZS_FAST=0: every zstd member through the wave decoder
-#ifdef RPGPU_NO_GZS                   // A/B variant (scripts/build_exp.py): every gzip member serial
-    bool gzs = false;
-#else
     bool gzs = true;                  // RPGPU_GZS=0: every gzip member serial
-#endif
     bool xxh_side = true;             // RPGPU_XXH_SIDE=0: the content checksums inside k_decode_finish
     uint32_t lzwalk_wgs = 0;          // RPGPU_LZWALK_WGS=n: k_lz_walk's grid in workgroups (0: 16 per CU)
     uint32_t walk_wgs = 8;            // RPGPU_WALK_WGS=n: k_walk's workgroups per CU

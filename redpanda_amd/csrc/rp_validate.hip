@@ -32,9 +32,11 @@ __device__ unsigned long long g_stamps[8];
 __shared__ unsigned long long s_stamps[kVWaves][8];  // per-wave, flushed once at the end
 #define STAMP(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #define STAMP_ADD(i, d) do { if (lane() == 0) s_stamps[threadIdx.x >> 6][i] += (unsigned long long)(d); } while (0)
+#define ST(...) __VA_ARGS__
 #else
 #define STAMP(v)
 #define STAMP_ADD(i, d)
+#define ST(...)
 #endif
 
 DEV uint32_t L32(const uint8_t* lds, uint32_t a) { return *(const uint32_t*)(lds + a); }
@@ -110,18 +112,11 @@ DEV uint32_t pick4(uint4 v, uint32_t k) {
 // One 16-byte row of the payload stream, loaded non-temporal: every byte is
 // read once per launch, and with the default policy the window stream
 // displaced lines other waves were still waiting on (measured on C1:
-// k_validate 3.20 -> 2.96 ms; RPGPU_NT_WINDOW=0 restores the default policy
-// for A/B).
-#ifndef RPGPU_NT_WINDOW
-#define RPGPU_NT_WINDOW 1
-#endif
+// k_validate 3.20 -> 2.96 ms).
 DEV uint4 ld_stream(const uint8_t* p) {
-    if (RPGPU_NT_WINDOW) {
-        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        const v4u v = __builtin_nontemporal_load((const v4u*)p);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    }
-    return *(const uint4*)p;
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const v4u v = __builtin_nontemporal_load((const v4u*)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
 }
 
 // A lane's share of the current window: dword k of row i in d[i] (rows
@@ -883,10 +878,7 @@ DEV void note_bad_lane(const J& j, uint32_t seg, uint64_t b) {
 // it (record k + 1's length .. value length).  5-row regions (48 / 32: 10 KiB
 // of LDS per wave, four workgroups per CU instead of three) measured slower
 // on C1 (walk 1.34 -> 1.49 ms): the walk is not short of walks in flight.
-#ifndef RPGPU_WALK_ROWS
-#define RPGPU_WALK_ROWS 6
-#endif
-constexpr uint32_t kRegionRows = RPGPU_WALK_ROWS;
+constexpr uint32_t kRegionRows = 6;
 constexpr uint32_t kRegionBytes = 16u * kRegionRows;
 constexpr uint32_t kRegionBefore = 48u;  // bytes of C_k before the 16-aligned guessed end
 static_assert(kRegionBytes > kRegionBefore && 64u * kRegionBytes >= 4096u, "region / staging geometry");
@@ -896,23 +888,15 @@ constexpr uint32_t kWalkLdsWave = 2u * kSlotBytes;
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
-#ifndef RPGPU_WALK_AUX
-#define RPGPU_WALK_AUX 2  // region fetch non-temporal (measured: walk 1.36 -> 1.30 ms); 0 = default policy
-#endif
+constexpr int kWalkAux = 2;  // region fetch non-temporal (measured: walk 1.36 -> 1.30 ms); 0 = default policy
 
 DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// Region layout in a slot.  Cooperative fetch (default): lane w's region is
-// contiguous at slot + 96 w.  Per-lane fetch (RPGPU_WALK_COOP_LOAD=0, kept
-// for A/B): each lane issues its own six global_load_lds, which land
-// lane-linear, so row r of lane w sits at slot + 1024 r + 16 w.  Measured on
-// C1: walk 1.36 ms cooperative, 1.45 ms per-lane.
-#ifndef RPGPU_WALK_COOP_LOAD
-#define RPGPU_WALK_COOP_LOAD 1
-#endif
-constexpr bool kCoopLoad = RPGPU_WALK_COOP_LOAD != 0;
-DEV uint32_t region_off(uint32_t o) { return kCoopLoad ? o : (o >> 4) * 1024u + (o & 12u); }
-DEV uint32_t region_lane(uint32_t l) { return kCoopLoad ? kRegionBytes * l : 16u * l; }
+// Region layout in a slot: lane w's region is contiguous at slot + 96 w (the
+// cooperative fetch below).  Each lane fetching its own rows, which land
+// lane-linear (row r of lane w at slot + 1024 r + 16 w), measured slower on
+// C1: walk 1.45 ms against 1.36 ms.
+DEV uint32_t region_lane(uint32_t l) { return kRegionBytes * l; }
 
 // rows of the region at grid offset base that start inside the payload
 // (the others are never parsed and are not loaded)
@@ -939,7 +923,7 @@ DEV void coop_load(uint8_t* slot, const uint8_t* g, uint32_t rows) {
         const uint32_t wnr = (uint32_t)__builtin_amdgcn_ds_bpermute(src, nr);
         if (r < wnr) {
             const uint8_t* row = (const uint8_t*)(uintptr_t)(((uint64_t)whi << 32) | wlo) + 16u * r;
-            __builtin_amdgcn_global_load_lds((gbl_void*)row, (lds_void*)(slot + 1024u * m), 16, 0, RPGPU_WALK_AUX);
+            __builtin_amdgcn_global_load_lds((gbl_void*)row, (lds_void*)(slot + 1024u * m), 16, 0, kWalkAux);
         }
     }
 }
@@ -950,9 +934,6 @@ DEV void coop_load(uint8_t* slot, const uint8_t* g, uint32_t rows) {
 // as 4 lanes x 16 contiguous bytes, instead of one 16-byte piece of each of
 // 64 scattered entries per instruction (the index stores were a third of
 // the walk's time).
-#ifndef RPGPU_NT_INDEX
-#define RPGPU_NT_INDEX 0  // index entries stored non-temporal (A/B knob)
-#endif
 DEV void coop_store(uint8_t* stage, const rpgpu_record_index& e, rpgpu_record_index* dst) {
     static_assert(sizeof(rpgpu_record_index) == 64, "index entry is 4 x 16 bytes");
     const uint32_t l = lane_v();
@@ -975,12 +956,7 @@ DEV void coop_store(uint8_t* stage, const rpgpu_record_index& e, rpgpu_record_in
         if (wlo | whi) {
             const uint4 v = *(const uint4*)(stage + 64u * w + 16u * qtr);
             uint4* d = (uint4*)((uint8_t*)(uintptr_t)(((uint64_t)whi << 32) | wlo) + 16u * qtr);
-            if (RPGPU_NT_INDEX) {
-                typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-                v4u x;
-                x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
-                __builtin_nontemporal_store(x, (v4u*)d);
-            } else *d = v;
+            *d = v;
         }
     }
 }
@@ -992,12 +968,12 @@ DEV void lane_region_load(const uint8_t* p0, uint32_t mis, uint32_t n, uint32_t 
     const uint32_t rows = region_rows(n, mis, base);
 #pragma unroll
     for (uint32_t r = 0; r < kRegionRows; r++)
-        if (r < rows) *(uint4*)(region + region_off(16u * r)) = *(const uint4*)(row + 16u * r);
+        if (r < rows) *(uint4*)(region + 16u * r) = *(const uint4*)(row + 16u * r);
 }
 
 // dword at 4-aligned offset o (< kRegionBytes) of a lane's region
 DEV uint32_t region_dw(const uint8_t* region, uint32_t o) {
-    return *(const uint32_t*)(region + region_off(o));
+    return *(const uint32_t*)(region + o);
 }
 
 // The record parser's byte source over LDS regions: the current region A,
@@ -1218,10 +1194,8 @@ __global__ __launch_bounds__(1024) void k_validate(DeviceJob j) {
     const uint64_t nb_total = j.chunk_count[j.total_chunks];
     const uint64_t nb = nb_total < j.batch_capacity ? nb_total : j.batch_capacity;
     const uint64_t nw = (uint64_t)gridDim.x * kVWaves;
-#ifdef RPGPU_STAMPS
-    if (l == 0)
-        for (int i = 0; i < 8; i++) s_stamps[tid >> 6][i] = 0;
-#endif
+    ST(if (l == 0)
+           for (int i = 0; i < 8; i++) s_stamps[tid >> 6][i] = 0;)
     STAMP(tk0);
     uint64_t b = (uint64_t)blockIdx.x * kVWaves + (tid >> 6);
     if (b < nb) {
@@ -1331,10 +1305,8 @@ __global__ __launch_bounds__(1024) void k_validate(DeviceJob j) {
     }
     STAMP(tk1);
     STAMP_ADD(4, tk1 - tk0);
-#ifdef RPGPU_STAMPS
-    if (l == 0)
-        for (int i = 0; i < 8; i++) atomicAdd(&g_stamps[i], s_stamps[tid >> 6][i]);
-#endif
+    ST(if (l == 0)
+           for (int i = 0; i < 8; i++) atomicAdd(&g_stamps[i], s_stamps[tid >> 6][i]);)
 }
 
 #ifdef RPGPU_STAMPS
@@ -1504,14 +1476,12 @@ __global__ __launch_bounds__(1024) void k_crc_compose(DeviceJob j) {
 // 0xFFFFFFFF where it stops (a start at or past the end, a bad length);
 // written at the payload's index slots of the record pool (j.dchain), read
 // back 64 at a time by walk_records (pre_starts).
-#ifndef RPGPU_DCHAIN_PRIO
-#define RPGPU_DCHAIN_PRIO 2
-#endif
+constexpr int kDchainPrio = 2;
 __global__ __launch_bounds__(256) void k_dchain(DeviceJob j) {
     // above k_content_xxh's waves on a shared SIMD: an XXH32 chain keeps the
     // SIMD's VALU busy back to back (its quarter-rate multiply per stripe), and
     // a chain lane waiting behind it held k_dchain's end with it (0.9 -> 1.9 ms)
-    __builtin_amdgcn_s_setprio(RPGPU_DCHAIN_PRIO);
+    __builtin_amdgcn_s_setprio(kDchainPrio);
     const uint32_t nlz = j.counters[2], ngz = j.counters[16], count = nlz + ngz + j.counters[19];
     const uint8_t* const aend = j.decoded + j.decoded_capacity;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
@@ -1672,14 +1642,7 @@ __global__ __launch_bounds__(256) void k_walk(DeviceJob j) {
         else if (st == kHead) want = w.h_base;
         if (st == kWalk || st == kHead) rows = region_rows(w.n, w.mis, want);
         if (__ballot(st != kFin) == 0) break;
-        if (kCoopLoad) coop_load(cslot, w.p0 - w.mis + want, rows);
-        else {
-            const uint8_t* g = w.p0 - w.mis + want;
-#pragma unroll
-            for (uint32_t r = 0; r < kRegionRows; r++)
-                if (r < rows)
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(g + 16u * r), (lds_void*)(cslot + 1024u * r), 16, 0, 0);
-        }
+        coop_load(cslot, w.p0 - w.mis + want, rows);
         wait_vm();
         rpgpu_record_index e;
         rpgpu_record_index* dst = nullptr;

@@ -2,6 +2,7 @@
 with an alternate kernel source (--unit, default rp_validate.hip) and/or extra defines; the other objects
 come from the main build.  Usage:
   python scripts/build_exp.py NAME [--src path/to/rp_validate.hip] [--unit rp_codec.hip] [--base diag] [-DFOO ...]
+The kernels' tuning numbers are plain constants, not -D switches: to vary one, edit a copy of the unit and pass it with --src.
 Load with RPGPU_VARIANT=NAME.  Diagnostics only, never the product."""
 import os
 import sys

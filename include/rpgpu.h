@@ -639,6 +639,142 @@ size_t rpgpu_compact_sizeof(int which);
  * call's last event. */
 int rpgpu_compact_timings(rpgpu_ctx* ctx, float* ms, int n);
 
+/* ------------------------------------------------------------------------ */
+/* Produce path: validated Kafka v2 record sets -> the bytes the log         */
+/* receives (kafka_batch_adapter::adapt, kafka/protocol/                     */
+/* kafka_batch_adapter.cc:32-91, :126-188; the partition verdict of          */
+/* kafka/server/handlers/produce.cc:364-412; set_max_timestamp for append    */
+/* time topics, produce.cc:223-232, model/record.h:598-608;                  */
+/* disk_log_appender::operator(), storage/disk_log_appender.cc:72-74,        */
+/* :113-119).                                                                */
+/* ------------------------------------------------------------------------ */
+/* rpgpu_append_set.status: what the produce handler answers for the
+ * partition.  Per batch the first failing test wins, in the order
+ * batch_reader::consume_batch / adapt() meet them:
+ *   not RPGPU_F_COMPLETE        MALFORMED        (share() / skip throws)
+ *   not RPGPU_F_WIRE_V2         CORRUPT_MESSAGE  (produce.cc:385 tests valid_crc before v2_format; the
+ *                                                 reference leaves valid_crc unset for a batch that is not v2,
+ *                                                 this surface pins it to false)
+ *   not RPGPU_F_CRC_OK          CORRUPT_MESSAGE
+ *   RPGPU_F_CODEC_INVALID       MALFORMED        (attrs.compression() throws out of adapt)
+ *   not compressed and not
+ *   RPGPU_F_PARSE_OK            INVALID_RECORD   (adapt leaves `batch` empty)
+ */
+enum rpgpu_append_status {
+    RPGPU_APPEND_OK = 0,
+    RPGPU_APPEND_CORRUPT_MESSAGE = 1,
+    RPGPU_APPEND_INVALID_RECORD = 2,
+    RPGPU_APPEND_MALFORMED = 3,
+    RPGPU_APPEND_SOURCE_OVERFLOW = 4, /* the source job's totals.overflow != 0: every set gets this */
+};
+
+/* rpgpu_append_job.flags.  Without it the produce rule holds: only the first
+ * batch on a set's chain is looked at and appended, whatever follows is
+ * ignored (adapt()'s remainder is dropped), and a set without a batch on its
+ * chain (empty, shorter than 61 bytes, batch_length + 12 < 61) is MALFORMED.
+ * With it, the loop of kafka/protocol/kafka_batch_adapter.h:44-49: every
+ * batch on the chain is appended in chain order; the set is accepted only if
+ * every batch is and the chain ended with RPGPU_ERRC_END_OF_STREAM (an empty
+ * set: the loop does not run, nothing is appended, status OK); otherwise its
+ * status is the first failing batch's, or MALFORMED for a bad terminal. */
+#define RPGPU_APPEND_ALL_BATCHES (1u << 0)
+
+/* d_append_time[s] for a topic with create time: batches keep their
+ * timestamps.  Any other value t applies set_max_timestamp(append_time, t). */
+#define RPGPU_APPEND_CREATE_TIME INT64_MIN
+
+/* Per record set (partition).  40 bytes. */
+typedef struct rpgpu_append_set {
+    uint32_t status;      /* rpgpu_append_status; not OK: nothing written, no offsets consumed */
+    uint32_t first_bad;   /* set-relative chain ordinal of the batch that decided the status, or the chain's
+                             batch count when no batch did (0 for SOURCE_OVERFLOW) */
+    uint64_t n_batches;   /* batches appended */
+    int64_t base_offset;  /* first offset assigned (= next_offset) */
+    int64_t last_offset;  /* last offset assigned; next_offset - 1 when nothing was appended: the produce
+                             response's value and, + 1, the next call's next_offset */
+    uint64_t bytes_out;
+} rpgpu_append_set;
+
+/* Whole call.  64 bytes. */
+typedef struct rpgpu_append_totals {
+    uint64_t sets_ok;
+    uint64_t batches_out;
+    uint64_t bytes_out;
+    uint64_t out_capacity_needed;        /* bytes_out + 16 */
+    uint64_t out_batch_capacity_needed;  /* batches_out */
+    uint32_t overflow;                   /* bit 0: out_capacity, bit 1: out_batch_capacity too small; nothing
+                                            is then written to d_out / d_out_batches */
+    uint32_t reserved0;
+    uint64_t reserved[2];
+} rpgpu_append_totals;
+
+/* All pointers are DEVICE pointers, caller-owned.  The first block is the
+ * input and the outputs of a completed RPGPU_LAYOUT_WIRE rpgpu_submit with at
+ * least RPGPU_JOB_CRC | RPGPU_JOB_PARSE (same stream, or synchronised); one
+ * segment of that job is one partition's record set. */
+typedef struct rpgpu_append_job {
+    const uint8_t* d_data;
+    const uint64_t* d_seg_offsets;       /* n_segments + 1 */
+    uint32_t n_segments;
+    uint32_t flags;                      /* RPGPU_APPEND_* */
+    const rpgpu_batch_result* d_batches;
+    uint64_t batch_capacity;             /* a bound of the source job's totals.n_batches (its batch_capacity, or
+                                            the total itself): sizes grids and scratch */
+    const rpgpu_segment_summary* d_summaries;
+    const rpgpu_job_totals* d_totals;
+    const int64_t* d_next_offset;        /* n_segments: each partition's appender _idx */
+    const int64_t* d_append_time;        /* n_segments, or NULL (every topic uses create time) */
+    /* outputs */
+    uint8_t* d_out;                      /* the accepted sets back to back, in set order; 16-byte aligned */
+    uint64_t out_capacity;               /* bytes, including 16 spare bytes past the last batch: the source
+                                            batches' size_bytes summed, plus 16, is always enough */
+    uint64_t* d_out_seg_offsets;         /* n_segments + 1: set s's bytes are [s, s + 1) */
+    rpgpu_batch_result* d_out_batches;   /* one per appended batch, in output order */
+    uint64_t out_batch_capacity;
+    rpgpu_segment_summary* d_out_summaries; /* n_segments */
+    rpgpu_append_set* d_sets;            /* n_segments */
+    rpgpu_append_totals* d_atotals;      /* one */
+} rpgpu_append_job;
+
+/* Every appended batch is its 61-byte little-endian disk header
+ * (storage/segment_appender_utils.cc:28-54) followed by its payload verbatim:
+ * header_crc = internal_header_only_crc of the final header, size_bytes =
+ * batch_length + 12, base_offset = the set's next_offset for its first batch
+ * and the previous base_offset + last_offset_delta + 1 after that, type 1
+ * (raft_data), crc as on the wire, attrs .. record_count byte-reversed.  For
+ * a set with an append time t every appended batch gets attrs bit 3 and
+ * max_timestamp = t, and crc (crc_record_batch) is recomputed before
+ * header_crc.
+ *
+ * d_out_batches[i] holds what a disk-layout rpgpu_submit over d_out /
+ * d_out_seg_offsets with the source job's flags reports for that batch,
+ * except: index_base and decoded_off keep the source entry's values (the
+ * source job's record index and decoded arena stay valid for the payload:
+ * record positions are payload-relative, but record_index.batch keeps the
+ * source ordinals, so rpgpu_compact over these outputs is not promised), and
+ * decoded_crc / decoded_header_crc are 0 (they describe decompress_batch's
+ * form of the batch, which the append does not produce).  d_out_summaries[s]
+ * is that job's summary of output segment s with n_records = 0 (the record
+ * index stays the source's); a rejected or empty set gets the summary of an
+ * empty segment.  Both feed rpgpu_segment_index and rpgpu_serialize_wire
+ * without another validation pass.
+ *
+ * Asynchronous on `stream`; never writes out of bounds: a capacity that is
+ * too small sets d_atotals->overflow and reports the sizes needed.  NULL or
+ * inconsistent arguments return RPGPU_E_INVALID without touching a device. */
+int rpgpu_append_wire(rpgpu_ctx* ctx, const rpgpu_append_job* job, void* stream);
+
+/* sizeof of the append structs as compiled into the library: 0 =
+ * rpgpu_append_set, 1 = rpgpu_append_totals, 2 = rpgpu_batch_result (the
+ * entries of d_out_batches), 3 = rpgpu_append_job (0 for any other value). */
+size_t rpgpu_append_sizeof(int which);
+
+/* Device time of the last timed rpgpu_append_wire (rpgpu_set_timing), in
+ * milliseconds: 0 = whole call, 1 = verdicts + sizes, 2 = scans + plan,
+ * 3 = copy, 4 = append-time stamp, 5 = output metadata.  Synchronises on the
+ * call's last event. */
+int rpgpu_append_timings(rpgpu_ctx* ctx, float* ms, int n);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -1060,8 +1060,8 @@ inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::
 // ---------------------------------------------------------------------------
 namespace kafka {
 
-// kafka/protocol/errors.h (the one code this path raises)
-enum class error_code : int16_t { none = 0, corrupt_message = 2 };
+// kafka/protocol/errors.h (the codes this path raises)
+enum class error_code : int16_t { none = 0, corrupt_message = 2, invalid_record = 87 };
 
 // kafka/protocol/exceptions.h
 struct exception : std::runtime_error {
@@ -1150,6 +1150,132 @@ private:
     size_t _i = 0;
     size_t _pos = 0;
 };
+
+// What the produce handler answers for one partition and what its log
+// receives (kafka/server/handlers/produce.cc:364-412 -> partition_append:
+// adapt(), set_max_timestamp for append-time topics, then
+// disk_log_appender::operator()).
+struct partition_append {
+    error_code error{error_code::none};
+    rpgpu_append_status status{RPGPU_APPEND_OK};
+    int64_t base_offset{0};          // first offset assigned (the produce response's base_offset)
+    int64_t last_offset{-1};         // next_offset - 1 when nothing was appended
+    std::vector<uint8_t> log_bytes;  // the batches as the segment appender writes them; empty when rejected
+};
+
+// The record sets of one produce request, one per partition, through the
+// device in one pass: rpgpu_submit (wire layout: CRC | PARSE) validates them,
+// rpgpu_append_wire turns every accepted set into log bytes with offsets
+// from next_offsets[i].  append_times[i] != RPGPU_APPEND_CREATE_TIME is the
+// broker timestamp of a topic with message.timestamp.type=LogAppendTime.
+// RPGPU_APPEND_MALFORMED answers corrupt_message, as
+// batch_reader::check_terminal does for a short header.  all_batches: every
+// batch of a set (the loop of kafka_batch_adapter.h:44-49) instead of the
+// produce rule's first one.
+inline std::vector<partition_append> produce_append(const std::vector<rpgpu::iobuf>& record_sets,
+                                                    const std::vector<int64_t>& next_offsets,
+                                                    const std::optional<std::vector<int64_t>>& append_times = std::nullopt,
+                                                    rpgpu::engine& e = rpgpu::engine::local(), bool all_batches = false) {
+    const size_t n = record_sets.size();
+    if (next_offsets.size() != n || (append_times && append_times->size() != n))
+        throw std::invalid_argument("produce_append: one next offset (and append time) per record set");
+    std::vector<partition_append> res(n);
+    if (n == 0) return res;
+    rpgpu_ctx* c = e.ctx();
+    std::vector<uint64_t> offs(n + 1, 0);
+    for (size_t i = 0; i < n; i++) offs[i + 1] = offs[i] + record_sets[i].size_bytes();
+    const size_t len = (size_t)offs[n];
+    std::vector<uint8_t> host(len);
+    for (size_t i = 0; i < n; i++)
+        if (!record_sets[i].empty()) std::memcpy(host.data() + offs[i], record_sets[i].data(), record_sets[i].size_bytes());
+    rpgpu::dev_buffer d_data(e, len + 16), d_offs(e, (n + 1) * 8), d_next(e, n * 8), d_time(e, n * 8);
+    e.check(rpgpu_memset(c, (uint8_t*)d_data.get() + len, 0, 16, nullptr), "rpgpu_memset");
+    if (len) e.check(rpgpu_memcpy_h2d(c, d_data.get(), host.data(), len, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_offs.get(), offs.data(), (n + 1) * 8, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_next.get(), next_offsets.data(), n * 8, nullptr), "rpgpu_memcpy_h2d");
+    if (append_times) e.check(rpgpu_memcpy_h2d(c, d_time.get(), append_times->data(), n * 8, nullptr), "rpgpu_memcpy_h2d");
+    rpgpu_job j{};
+    j.d_data = (const uint8_t*)d_data.get();
+    j.d_seg_offsets = (const uint64_t*)d_offs.get();
+    j.h_seg_offsets = offs.data();
+    j.n_segments = (uint32_t)n;
+    j.layout = RPGPU_LAYOUT_WIRE;
+    j.flags = RPGPU_JOB_CRC | RPGPU_JOB_PARSE;
+    rpgpu_capacity cap{};
+    e.check(rpgpu_query_capacity(c, &j, nullptr, &cap), "rpgpu_query_capacity");
+    const uint64_t nb = cap.n_batches + 1, nr = cap.record_capacity + 1;
+    rpgpu::dev_buffer d_b(e, nb * sizeof(rpgpu_batch_result)), d_r(e, nr * sizeof(rpgpu_record_index)),
+        d_sum(e, n * sizeof(rpgpu_segment_summary)), d_tot(e, sizeof(rpgpu_job_totals));
+    j.d_batches = (rpgpu_batch_result*)d_b.get();
+    j.batch_capacity = nb;
+    j.d_records = (rpgpu_record_index*)d_r.get();
+    j.record_capacity = nr;
+    j.d_summaries = (rpgpu_segment_summary*)d_sum.get();
+    j.d_totals = (rpgpu_job_totals*)d_tot.get();
+    e.check(rpgpu_submit(c, &j, nullptr), "rpgpu_submit");
+    // every batch on the wire fits the bytes it came in: len + 16 is always enough
+    uint64_t out_cap = (uint64_t)len + 16, out_batches = nb;
+    rpgpu_append_totals at{};
+    std::vector<rpgpu_append_set> sets(n);
+    std::vector<uint64_t> out_offs(n + 1);
+    std::vector<uint8_t> bytes;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        rpgpu::dev_buffer d_out(e, out_cap), d_oso(e, (n + 1) * 8), d_ob(e, (out_batches + 1) * sizeof(rpgpu_batch_result)),
+            d_osum(e, n * sizeof(rpgpu_segment_summary)), d_sets(e, n * sizeof(rpgpu_append_set)),
+            d_at(e, sizeof(rpgpu_append_totals));
+        rpgpu_append_job k{};
+        k.d_data = j.d_data;
+        k.d_seg_offsets = j.d_seg_offsets;
+        k.n_segments = (uint32_t)n;
+        k.flags = all_batches ? RPGPU_APPEND_ALL_BATCHES : 0u;
+        k.d_batches = j.d_batches;
+        k.batch_capacity = nb;
+        k.d_summaries = j.d_summaries;
+        k.d_totals = j.d_totals;
+        k.d_next_offset = (const int64_t*)d_next.get();
+        k.d_append_time = append_times ? (const int64_t*)d_time.get() : nullptr;
+        k.d_out = (uint8_t*)d_out.get();
+        k.out_capacity = out_cap;
+        k.d_out_seg_offsets = (uint64_t*)d_oso.get();
+        k.d_out_batches = (rpgpu_batch_result*)d_ob.get();
+        k.out_batch_capacity = out_batches;
+        k.d_out_summaries = (rpgpu_segment_summary*)d_osum.get();
+        k.d_sets = (rpgpu_append_set*)d_sets.get();
+        k.d_atotals = (rpgpu_append_totals*)d_at.get();
+        e.check(rpgpu_append_wire(c, &k, nullptr), "rpgpu_append_wire");
+        e.check(rpgpu_memcpy_d2h(c, &at, d_at.get(), sizeof at, nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_memcpy_d2h(c, sets.data(), d_sets.get(), n * sizeof(rpgpu_append_set), nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_memcpy_d2h(c, out_offs.data(), d_oso.get(), (n + 1) * 8, nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        if (at.overflow) {
+            if (attempt) throw std::runtime_error("produce_append: output capacity");
+            out_cap = at.out_capacity_needed;
+            out_batches = at.out_batch_capacity_needed;
+            continue;
+        }
+        bytes.resize((size_t)at.bytes_out);
+        if (!bytes.empty()) {
+            e.check(rpgpu_memcpy_d2h(c, bytes.data(), d_out.get(), bytes.size(), nullptr), "rpgpu_memcpy_d2h");
+            e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        }
+        break;
+    }
+    for (size_t i = 0; i < n; i++) {
+        partition_append& p = res[i];
+        p.status = static_cast<rpgpu_append_status>(sets[i].status);
+        switch (p.status) {
+        case RPGPU_APPEND_OK: p.error = error_code::none; break;
+        case RPGPU_APPEND_INVALID_RECORD: p.error = error_code::invalid_record; break;
+        case RPGPU_APPEND_CORRUPT_MESSAGE:
+        case RPGPU_APPEND_MALFORMED: p.error = error_code::corrupt_message; break;
+        default: throw std::runtime_error("produce_append: the validation job overflowed its outputs");
+        }
+        p.base_offset = sets[i].base_offset;
+        p.last_offset = sets[i].last_offset;
+        p.log_bytes.assign(bytes.begin() + (ptrdiff_t)out_offs[i], bytes.begin() + (ptrdiff_t)out_offs[i + 1]);
+    }
+    return res;
+}
 
 }  // namespace kafka
 

@@ -54,6 +54,19 @@ class CompactJobC(C.Structure):
     ]
 
 
+class AppendJobC(C.Structure):
+    """rpgpu_append_job (include/rpgpu.h)."""
+    _fields_ = [
+        ("d_data", C.c_void_p), ("d_seg_offsets", C.c_void_p), ("n_segments", C.c_uint32), ("flags", C.c_uint32),
+        ("d_batches", C.c_void_p), ("batch_capacity", C.c_uint64),
+        ("d_summaries", C.c_void_p), ("d_totals", C.c_void_p),
+        ("d_next_offset", C.c_void_p), ("d_append_time", C.c_void_p),
+        ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("d_out_seg_offsets", C.c_void_p),
+        ("d_out_batches", C.c_void_p), ("out_batch_capacity", C.c_uint64),
+        ("d_out_summaries", C.c_void_p), ("d_sets", C.c_void_p), ("d_atotals", C.c_void_p),
+    ]
+
+
 def exported_symbols_from_header(path: str = HEADER):
     """Function names declared in include/rpgpu.h."""
     src = open(path).read()
@@ -120,6 +133,9 @@ def load():
         "rpgpu_compact": (i32, [vp, C.POINTER(CompactJobC), vp]),
         "rpgpu_compact_sizeof": (sz, [i32]),
         "rpgpu_compact_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
+        "rpgpu_append_wire": (i32, [vp, C.POINTER(AppendJobC), vp]),
+        "rpgpu_append_sizeof": (sz, [i32]),
+        "rpgpu_append_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -148,5 +164,5 @@ def crc32c(data, crc: int = 0) -> int:
     return load().rpgpu_crc32c_extend(crc, a.ctypes.data_as(C.c_void_p), a.nbytes)
 
 
-__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "RpgpuError", "abi",
+__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "AppendJobC", "RpgpuError", "abi",
            "exported_symbols_from_header"]

@@ -124,6 +124,26 @@ COMPACT_SEGMENT_COMPARE_FIELDS = [n for n in COMPACT_SEGMENT.names if n != "rese
 # key_compare_mismatches counts work (it depends on the insertion order), not a result
 COMPACT_TOTALS_COMPARE_FIELDS = [n for n in COMPACT_TOTALS.names if n not in ("reserved", "key_compare_mismatches")]
 
+# rpgpu_append_wire (include/rpgpu.h): produce-path append of wire record sets
+APPEND_OK, APPEND_CORRUPT_MESSAGE, APPEND_INVALID_RECORD, APPEND_MALFORMED, APPEND_SOURCE_OVERFLOW = 0, 1, 2, 3, 4
+APPEND_ALL_BATCHES = 1 << 0
+APPEND_CREATE_TIME = -(1 << 63)  # INT64_MIN: the topic uses create time
+
+APPEND_SET = np.dtype([
+    ("status", "<u4"), ("first_bad", "<u4"), ("n_batches", "<u8"), ("base_offset", "<i8"), ("last_offset", "<i8"),
+    ("bytes_out", "<u8"),
+])
+assert APPEND_SET.itemsize == 40
+APPEND_TOTALS = np.dtype([
+    ("sets_ok", "<u8"), ("batches_out", "<u8"), ("bytes_out", "<u8"), ("out_capacity_needed", "<u8"),
+    ("out_batch_capacity_needed", "<u8"), ("overflow", "<u4"), ("reserved0", "<u4"), ("reserved", "<u8", (2,)),
+])
+assert APPEND_TOTALS.itemsize == 64
+APPEND_SET_COMPARE_FIELDS = list(APPEND_SET.names)
+APPEND_TOTALS_COMPARE_FIELDS = [n for n in APPEND_TOTALS.names if not n.startswith("reserved")]
+# d_out_summaries: n_records is 0 by contract (the record index stays the source job's)
+APPEND_SUMMARY_COMPARE_FIELDS = [n for n in SEGMENT_SUMMARY.names if n != "reserved"]
+
 # fields of rpgpu_batch_result that are outputs of the engine and compared
 # bit-exactly against the oracle (reserved fields excluded)
 BATCH_COMPARE_FIELDS = [n for n in BATCH_RESULT.names if not n.startswith("reserved")]

@@ -468,4 +468,27 @@ hipError_t launch_compact_size(const CompactArgs& a, uint32_t cus, hipStream_t s
 hipError_t launch_compact_plan(const CompactArgs& a, hipStream_t s);  // after the scans: segments, totals, overflow
 hipError_t launch_compact_write(const CompactArgs& a, uint32_t cus, hipStream_t s);
 
+// rp_append.hip: produce-path append (rpgpu_append_wire).  Workspace arrays
+// are context scratch; nb bounds the source job's batch total.
+// Payloads are copied in pieces of kAppendPiece bytes, one wave each (a
+// starting guess, not a measured value).
+constexpr uint32_t kAppendPiece = 65536;
+struct AppendArgs {
+    rpgpu_append_job job;
+    uint64_t nb;              // job.batch_capacity
+    uint32_t* seg_bad;        // n_segments: first failing chain ordinal of each set (atomicMin; ~0u = none)
+    uint32_t* verdict;        // nb: rpgpu_append_status of each source batch
+    uint64_t* bpos;           // nb + 1: output bytes per source batch (0: not appended) -> exclusive scan
+    uint64_t* bcnt;           // nb + 1: low half 1 per appended batch, high half its copy pieces -> exclusive scan
+    uint64_t* bstep;          // nb + 1: offset step (last_offset_delta + 1) per appended batch -> exclusive scan
+    uint64_t* spos;           // nb: rpgpu_stamp positions of the append-time batches
+    uint32_t* splen;          // nb: their payload lengths
+    uint32_t* counters;       // [0] append-time batches to stamp, [1] k_stamp's claim cursor
+    const Tables* tables;
+};
+hipError_t launch_append_sizes(const AppendArgs& a, hipStream_t s);   // verdicts, then sizes / counts / steps
+hipError_t launch_append_plan(const AppendArgs& a, hipStream_t s);    // after the scans: sets, summaries, totals
+hipError_t launch_append_copy(const AppendArgs& a, uint32_t cus, hipStream_t s);
+hipError_t launch_append_meta(const AppendArgs& a, hipStream_t s);    // after the stamp: d_out_batches
+
 }  // namespace rp

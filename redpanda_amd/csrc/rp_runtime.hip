@@ -142,6 +142,11 @@ struct rpgpu_ctx {
     Buf cws;
     hipEvent_t cev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool cev_live = false;
+    // rpgpu_append_wire workspace (verdicts, per-batch plan, scan temporaries,
+    // the append-time stamp list); its stage events (rpgpu_set_timing)
+    Buf aws;
+    hipEvent_t aev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool aev_live = false;
     // k_lz_exec parse records (kRecsPerLane per lane of each resident wave),
     // allocated on the first decode job
     Buf seqs;
@@ -450,7 +455,7 @@ int rpgpu_destroy(rpgpu_ctx* c) {
         if (sd->join_ev) (void)hipEventDestroy(sd->join_ev);
     }
     if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
-    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->seqs, &c->pool, &c->fpool,
+    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->seqs, &c->pool, &c->fpool,
                    &c->sth, &c->std_, &c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h,
                    &c->hc_small, &c->gz_pool, &c->gzs_pool})
         b->release();
@@ -463,6 +468,8 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     }
     if (c->d_tables) hipFree(c->d_tables);
     for (hipEvent_t e : c->cev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->aev)
         if (e) hipEventDestroy(e);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     for (auto& set : c->ev_sets)
@@ -1467,6 +1474,114 @@ int rpgpu_compact_timings(rpgpu_ctx* c, float* ms, int n) {
     float v[6] = {0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipEventElapsedTime(&v[0], c->cev[0], c->cev[5]));
     for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->cev[i - 1], c->cev[i]));
+    for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
+    return RPGPU_OK;
+}
+
+// The produce path's append over a completed wire-layout job's outputs
+// (kernels in rp_append.hip).
+size_t rpgpu_append_sizeof(int which) {
+    switch (which) {
+    case 0: return sizeof(rpgpu_append_set);
+    case 1: return sizeof(rpgpu_append_totals);
+    case 2: return sizeof(rpgpu_batch_result);
+    case 3: return sizeof(rpgpu_append_job);
+    default: return 0;
+    }
+}
+
+int rpgpu_append_wire(rpgpu_ctx* c, const rpgpu_append_job* job, void* stream) {
+    if (!c || !job) return RPGPU_E_INVALID;
+    if (!job->d_totals || !job->d_atotals || !job->d_out_seg_offsets)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: missing argument");
+    if (job->n_segments && (!job->d_seg_offsets || !job->d_summaries || !job->d_next_offset || !job->d_sets ||
+                            !job->d_out_summaries))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: missing set arrays");
+    if (job->batch_capacity && (!job->d_batches || !job->d_data))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: missing job outputs");
+    if ((job->out_capacity && !job->d_out) || (job->out_batch_capacity && !job->d_out_batches))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: missing output buffer");
+    if (((uintptr_t)job->d_out & 15) != 0)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: d_out must be 16-byte aligned");
+    if (job->flags & ~RPGPU_APPEND_ALL_BATCHES) return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: unknown flag");
+    // batch ordinals and copy pieces are counted in 32 bits
+    if (job->batch_capacity >= 0x7FFFFFFFull || job->n_segments > 0x7FFFFFFFu ||
+        job->out_capacity / kAppendPiece >= 0x7FFFFFFFull)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_append_wire: capacity out of range");
+    hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    const uint64_t nb = job->batch_capacity, nseg = job->n_segments;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t o = need; need += align_up(bytes, 256); return o; };
+    const size_t o_bad = take(nseg * 4), o_verdict = take(nb * 4), o_bpos = take((nb + 1) * 8), o_bcnt = take((nb + 1) * 8);
+    const size_t o_bstep = take((nb + 1) * 8), o_spos = take(nb * 8), o_splen = take(nb * 4);
+    const size_t o_scan = take(scan_temp_bytes(nb) + 64), o_cnt = take(256);
+    need += 256;
+    if (int rc = grow(c, c->aws, need, s, "rpgpu_append_wire workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->aws.as<uint8_t>();
+    AppendArgs a;
+    a.job = *job;
+    a.nb = nb;
+    a.seg_bad = (uint32_t*)(w + o_bad);
+    a.verdict = (uint32_t*)(w + o_verdict);
+    a.bpos = (uint64_t*)(w + o_bpos);
+    a.bcnt = (uint64_t*)(w + o_bcnt);
+    a.bstep = (uint64_t*)(w + o_bstep);
+    a.spos = (uint64_t*)(w + o_spos);
+    a.splen = (uint32_t*)(w + o_splen);
+    a.counters = (uint32_t*)(w + o_cnt);
+    a.tables = c->d_tables;
+    const bool timed = c->timing;
+    auto mark = [&](int i) -> hipError_t {
+        if (!timed) return hipSuccess;
+        if (!c->aev[i]) {
+            hipError_t e = hipEventCreate(&c->aev[i]);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(c->aev[i], s);
+    };
+    c->aev_live = false;
+    HIPCHK(c, mark(0));
+    if (nseg) HIPCHK(c, hipMemsetAsync(a.seg_bad, 0xFF, nseg * 4, s));
+    HIPCHK(c, hipMemsetAsync(a.counters, 0, 256, s));
+    // the scans leave the totals at [nb]; without batches these are the totals
+    HIPCHK(c, hipMemsetAsync(a.bpos + nb, 0, 8, s));
+    HIPCHK(c, hipMemsetAsync(a.bcnt + nb, 0, 8, s));
+    HIPCHK(c, hipMemsetAsync(a.bstep + nb, 0, 8, s));
+    HIPCHK(c, hipMemsetAsync(job->d_atotals, 0, sizeof(rpgpu_append_totals), s));
+    if (nb) HIPCHK(c, launch_append_sizes(a, s));
+    HIPCHK(c, mark(1));
+    if (nb) {
+        HIPCHK(c, scan_exclusive_u64(a.bpos, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+        HIPCHK(c, scan_exclusive_u64(a.bcnt, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+        HIPCHK(c, scan_exclusive_u64(a.bstep, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+    }
+    HIPCHK(c, launch_append_plan(a, s));
+    HIPCHK(c, mark(2));
+    if (nb) HIPCHK(c, launch_append_copy(a, c->cu_count, s));
+    HIPCHK(c, mark(3));
+    // set_max_timestamp changed attrs / max_timestamp of the append-time
+    // batches: crc_record_batch again, then header_crc (model/record.h:598-608)
+    const uint64_t nstamp = std::min<uint64_t>(nb, job->out_batch_capacity);
+    if (nstamp && job->d_append_time)
+        HIPCHK(c, launch_stamp(job->d_out, a.spos, a.splen, nullptr, 0, (uint32_t)nstamp, RPGPU_STAMP_CRC, c->d_tables,
+                               a.counters + 1, c->cu_count, s, a.counters));
+    HIPCHK(c, mark(4));
+    if (nb) HIPCHK(c, launch_append_meta(a, s));
+    HIPCHK(c, mark(5));
+    c->aev_live = timed;
+    return scratch.release();
+}
+
+int rpgpu_append_timings(rpgpu_ctx* c, float* ms, int n) {
+    if (!c || !ms) return RPGPU_E_INVALID;
+    if (!c->aev_live) return fail(c, RPGPU_E_INVALID, "rpgpu_append_timings: no timed rpgpu_append_wire");
+    HIPCHK(c, hipEventSynchronize(c->aev[5]));
+    float v[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventElapsedTime(&v[0], c->aev[0], c->aev[5]));
+    for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->aev[i - 1], c->aev[i]));
     for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
     return RPGPU_OK;
 }

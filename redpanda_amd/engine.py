@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from ._lib import CapacityC, CompactJobC, JobC, RpgpuError, check, load
+from ._lib import AppendJobC, CapacityC, CompactJobC, JobC, RpgpuError, check, load
 
 
 def _torch():
@@ -94,6 +94,58 @@ class HostCompactResult:
     out_seg_offsets: np.ndarray
     batches: np.ndarray
     segments: np.ndarray
+    totals: np.void
+
+
+@dataclass
+class AppendResult:
+    """Device outputs of Engine.append_wire (rpgpu_append_wire).  `batches`,
+    `summaries`, `n_segments` and totals_host() have DeviceResult's shape, so
+    Engine.segment_index and Engine.serialize_wire (over `out` and
+    `out_seg_offsets`) take an AppendResult where they take a disk-layout
+    job's outputs."""
+    out: "object"              # uint8 tensor: the accepted sets' log bytes back to back
+    out_seg_offsets: "object"  # int64 tensor, n_segments + 1
+    batches: "object"          # uint8 tensor viewed as abi.BATCH_RESULT on the host
+    summaries: "object"        # uint8 tensor viewed as abi.SEGMENT_SUMMARY
+    sets: "object"             # uint8 tensor viewed as abi.APPEND_SET
+    atotals: "object"          # uint8 tensor viewed as abi.APPEND_TOTALS
+    n_segments: int
+
+    def append_totals_host(self):
+        return np.frombuffer(self.atotals.cpu().numpy().tobytes(), dtype=abi.APPEND_TOTALS)[0]
+
+    def totals_host(self):
+        """The rpgpu_job_totals a disk-layout job over the output would report
+        (n_batches; no records: the record index stays the source job's)."""
+        a = self.append_totals_host()
+        t = np.zeros(1, dtype=abi.JOB_TOTALS)[0]
+        nb = 0 if a["overflow"] else int(a["batches_out"])
+        t["n_batches"] = t["batch_capacity_needed"] = nb
+        return t
+
+    def to_host(self):
+        t = self.append_totals_host()
+        ok = not t["overflow"]
+        nb = int(t["batches_out"]) if ok else 0
+        nby = int(t["bytes_out"]) if ok else 0
+        return HostAppendResult(
+            out=self.out[:nby].cpu().numpy(),
+            out_seg_offsets=self.out_seg_offsets.cpu().numpy().view(np.uint64),
+            batches=np.frombuffer(self.batches[: nb * abi.BATCH_RESULT.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.BATCH_RESULT),
+            summaries=np.frombuffer(self.summaries.cpu().numpy().tobytes(), dtype=abi.SEGMENT_SUMMARY)[: self.n_segments],
+            sets=np.frombuffer(self.sets.cpu().numpy().tobytes(), dtype=abi.APPEND_SET)[: self.n_segments],
+            totals=t)
+
+
+@dataclass
+class HostAppendResult:
+    out: np.ndarray
+    out_seg_offsets: np.ndarray
+    batches: np.ndarray
+    summaries: np.ndarray
+    sets: np.ndarray
     totals: np.void
 
 
@@ -455,6 +507,97 @@ class Engine:
             out_capacity = int(ct["out_capacity_needed"])
             out_batch_capacity = int(ct["out_batch_capacity_needed"])
         return res
+
+    def append_wire(self, data, seg_offsets, out: DeviceResult, next_offsets, append_times=None,
+                    all_batches: bool = False, stream=None, out_capacity: int = None, out_batch_capacity: int = None,
+                    sync: bool = True, out_buffer=None) -> "AppendResult":
+        """rpgpu_append_wire: the log bytes of the record sets of a completed
+        wire-layout job `out` (at least JOB_CRC | JOB_PARSE over `data`, a
+        torch uint8 CUDA tensor; one segment = one partition's record set):
+        per accepted set its batches with disk headers, offsets assigned from
+        next_offsets[s], and set_max_timestamp applied where append_times[s]
+        is not abi.APPEND_CREATE_TIME (append_times=None: create time
+        everywhere).  all_batches=False is the produce rule (the first batch
+        of each set only).  Returns device tensors; .to_host() gives numpy
+        views.  The capacities default to what always fits (the source
+        batches' size_bytes summed plus 16; the source batch count); a call
+        whose capacity turns out too small is retried once with the sizes
+        the device reported (sync=False skips that check and the retry).
+        out_buffer: a 16-byte aligned uint8 CUDA tensor of at least
+        out_capacity bytes to write the first attempt into."""
+        torch = _torch()
+        dev = data.device
+        t = out.totals_host()
+        nb = int(min(t["n_batches"], out.batches.numel() // abi.BATCH_RESULT.itemsize))
+        nseg = out.n_segments
+        h_off = np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.uint64))
+        d_off = torch.from_numpy(h_off.view(np.int64)).to(dev)
+        nxt = np.zeros(max(nseg, 1), dtype=np.int64)
+        nxt[:nseg] = np.asarray(next_offsets, dtype=np.int64)
+        d_next = torch.from_numpy(nxt).to(dev)
+        d_time = None
+        if append_times is not None:
+            at = np.full(max(nseg, 1), abi.APPEND_CREATE_TIME, dtype=np.int64)
+            at[:nseg] = np.asarray(append_times, dtype=np.int64)
+            d_time = torch.from_numpy(at).to(dev)
+        if out_capacity is None:
+            b = np.frombuffer(out.batches[: nb * abi.BATCH_RESULT.itemsize].cpu().numpy().tobytes(), dtype=abi.BATCH_RESULT)
+            out_capacity = int(np.sum(np.maximum(b["size_bytes"].astype(np.int64), 0))) + 16
+        if out_batch_capacity is None:
+            out_batch_capacity = nb
+        u8 = torch.uint8
+        seg_off = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+        sums = torch.zeros(max(nseg, 1) * abi.SEGMENT_SUMMARY.itemsize, dtype=u8, device=dev)
+        sets = torch.zeros(max(nseg, 1) * abi.APPEND_SET.itemsize, dtype=u8, device=dev)
+        tot = torch.zeros(abi.APPEND_TOTALS.itemsize, dtype=u8, device=dev)
+        for attempt in range(2):
+            if out_buffer is not None and attempt == 0:
+                if out_buffer.numel() < out_capacity:
+                    raise RpgpuError("append_wire: out_buffer smaller than out_capacity")
+                obuf = out_buffer
+            else:
+                obuf = torch.zeros(max(out_capacity, 16), dtype=u8, device=dev)
+            obat = torch.zeros(max(out_batch_capacity, 1) * abi.BATCH_RESULT.itemsize, dtype=u8, device=dev)
+            job = AppendJobC()
+            job.d_data = data.data_ptr()
+            job.d_seg_offsets = d_off.data_ptr()
+            job.n_segments = nseg
+            job.flags = abi.APPEND_ALL_BATCHES if all_batches else 0
+            job.d_batches = out.batches.data_ptr()
+            job.batch_capacity = nb
+            job.d_summaries = out.summaries.data_ptr()
+            job.d_totals = out.totals.data_ptr()
+            job.d_next_offset = d_next.data_ptr()
+            job.d_append_time = d_time.data_ptr() if d_time is not None else None
+            job.d_out = obuf.data_ptr()
+            job.out_capacity = out_capacity
+            job.d_out_seg_offsets = seg_off.data_ptr()
+            job.d_out_batches = obat.data_ptr()
+            job.out_batch_capacity = out_batch_capacity
+            job.d_out_summaries = sums.data_ptr()
+            job.d_sets = sets.data_ptr()
+            job.d_atotals = tot.data_ptr()
+            s, finish = self._stream(dev, stream)
+            check(self.L.rpgpu_append_wire(self.ctx, C.byref(job), C.c_void_p(s.cuda_stream)), self.ctx,
+                  "rpgpu_append_wire")
+            finish(data, d_off, out.batches, out.summaries, out.totals, d_next, d_time, obuf, seg_off, obat, sums, sets,
+                   tot)
+            res = AppendResult(obuf, seg_off, obat, sums, sets, tot, nseg)
+            if not sync:
+                return res
+            s.synchronize()
+            at_ = res.append_totals_host()
+            if not at_["overflow"] or attempt:
+                return res
+            out_capacity = int(at_["out_capacity_needed"])
+            out_batch_capacity = int(at_["out_batch_capacity_needed"])
+        return res
+
+    def append_timings(self):
+        """Device milliseconds of the last rpgpu_append_wire run under set_timing()."""
+        ms = (C.c_float * 6)()
+        check(self.L.rpgpu_append_timings(self.ctx, ms, 6), self.ctx, "rpgpu_append_timings")
+        return {"total": ms[0], "verdict_sizes": ms[1], "scan_plan": ms[2], "copy": ms[3], "stamp": ms[4], "meta": ms[5]}
 
     def compact_timings(self):
         """Device milliseconds of the last rpgpu_compact run under set_timing()."""

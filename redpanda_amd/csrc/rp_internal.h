@@ -275,7 +275,8 @@ struct DeviceJob {
                                   // [47] lzf_tail count; [12] k_crc_compose claim cursor, [24..25] bytes
                                   // k_raw_copy copied (u64), [44] k_decode_finish's checksummed-frame claim cursor,
                                   // [27] zstd members for k_zexact, [31] k_zexact's buffers (pool offset / 16 + 1),
-                                  // [48] / [49] k_members_first's claim cursors of its pass 2
+                                  // [48] / [49] k_members_first's claim cursors of its pass 2,
+                                  // [50] crcs k_crc_compose stored (RPGPU_DIAG builds only)
     uint32_t* decode_list;        // batch_capacity: ordinals of batches to uncompress
     uint32_t* seq_list;           // batch_capacity: decode items decoded whole by one lane
     uint32_t* link_list;          // batch_capacity: decode items whose linked LZ4F blocks one wave decodes in order

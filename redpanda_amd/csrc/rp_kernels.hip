@@ -844,6 +844,11 @@ __global__ void k_finalize_totals(DeviceJob j) {
     t.overflow = ov;
     t.n_rewalks = j.counters[0];
     t.reserved[0] = t.reserved[1] = 0;
+#ifdef RPGPU_DIAG
+    // the diagnostic build shows that the split and compose paths ran: payloads
+    // listed for k_crc_split (low half), crcs k_crc_compose stored (high half)
+    t.reserved[0] = (uint64_t)j.counters[3] | ((uint64_t)j.counters[50] << 32);
+#endif
     *j.totals = t;
 }
 

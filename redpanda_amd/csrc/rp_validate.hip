@@ -1463,6 +1463,9 @@ __global__ __launch_bounds__(1024) void k_crc_compose(DeviceJob j) {
             rpgpu_batch_result* R = &j.batches[b];
             R->crc_computed = ~state;
             R->reserved0 = (uint16_t)(R->reserved0 | 2u);
+#ifdef RPGPU_DIAG
+            atomicAdd(&j.counters[50], 1u);  // reported by k_finalize_totals (tests/diag_cases.py)
+#endif
         }
     }
 }

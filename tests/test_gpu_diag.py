@@ -2,8 +2,9 @@
 (tests/diag_cases.py): the gzip / zstd first-pass pool exhausted by hostile
 ISIZE trailers, RPGPU_JOB_HOST_CODECS without a loadable libzstd, and the
 LZ4 fast-path record pool cut so that listed and walked blocks mix, zstd
-ring-mode members through the wave decoder alone, and each alternative launch
-path a diagnostic switch still selects."""
+ring-mode members through the wave decoder alone, each alternative launch
+path a diagnostic switch still selects, and the split and compose CRC paths at
+small shapes, with the counts that show they ran."""
 import os
 import subprocess
 import sys
@@ -48,3 +49,19 @@ def test_path_switch_off_matches_oracle(switch):
     """The launch-path switches that stay: each alternative path
     on one small job of every codec."""
     assert f"path_switch {switch}=0 ok" in _run("path_switch", **{switch: "0"})
+
+
+def test_crc_split_small_shapes():
+    """k_crc_split / k_crc_combine on payloads from 1 KiB (RPGPU_SPLIT_MIN_KIB=1);
+    the diagnostic build's split count shows that they ran."""
+    out = _run("crc_split_small", RPGPU_SPLIT_MIN_KIB="1")
+    print(out.strip())
+    assert "crc_split_small ok" in out
+
+
+def test_crc_compose_small_shapes():
+    """k_crc_compose on frames of two raw blocks around short and long gaps;
+    the diagnostic build's compose count shows that it ran."""
+    out = _run("crc_compose_small")
+    print(out.strip())
+    assert "crc_compose_small ok" in out

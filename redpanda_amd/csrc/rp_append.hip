@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void k_append_copy(AppendArgs a) {
             if (l < 4) d = (hc >> (8 * l)) & 0xFFu;
             if (l < RPGPU_HEADER_SIZE) dst[l] = (uint8_t)d;
             if (stamped && l == 0) {
-                const uint32_t i = atomicAdd(&a.counters[0], 1u);
+                const uint32_t i = atomicAdd(&a.counters[kAcStampCount], 1u);
                 a.spos[i] = op;
                 a.splen[i] = plen;
             }

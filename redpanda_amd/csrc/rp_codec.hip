@@ -984,11 +984,11 @@ DEV bool piece_wave_walked(uint32_t kind, uint32_t csize, uint32_t cap, bool few
 // would claim one wave-wide atomic apiece only to skip)
 DEV void note_longs(const DeviceJob& j, uint32_t base, uint64_t m, uint64_t w) {
     if (m) {
-        uint32_t at = atomicAdd(&j.counters[11], (uint32_t)__builtin_popcountll(m));
+        uint32_t at = atomicAdd(&j.counters[kCtrLongCount], (uint32_t)__builtin_popcountll(m));
         for (; m; m &= m - 1) j.long_list[at++] = base + (uint32_t)__builtin_ctzll(m);
     }
     if (w) {
-        uint32_t at = atomicAdd(&j.counters[38], (uint32_t)__builtin_popcountll(w));
+        uint32_t at = atomicAdd(&j.counters[kCtrWlongCount], (uint32_t)__builtin_popcountll(w));
         for (; w; w &= w - 1) j.wlong_list[at++] = base + (uint32_t)__builtin_ctzll(w);
     }
 }
@@ -1012,10 +1012,10 @@ DEV uint32_t lzf_reserve(uint32_t csize) { return csize / 3 + 2; }
 // hold stays with k_lz_walk.  Returns the blocks listed.
 DEV uint64_t note_fast(const DeviceJob& j, uint32_t base, uint64_t m, uint32_t res) {
     if (!m || !j.lzf_list || !j.frecs) return 0;
-    const uint64_t fb = atomicAdd((unsigned long long*)(j.counters + 42), (unsigned long long)res);
+    const uint64_t fb = atomicAdd((unsigned long long*)(j.counters + kCtrFrecsUsed64), (unsigned long long)res);
     if (fb + res > j.frec_cap) return 0;
     const uint64_t listed = m;
-    uint32_t at = atomicAdd(&j.counters[45], (uint32_t)__builtin_popcountll(m));
+    uint32_t at = atomicAdd(&j.counters[kCtrLzfCount], (uint32_t)__builtin_popcountll(m));
     for (; m; m &= m - 1) {
         const uint32_t p = base + (uint32_t)__builtin_ctzll(m);
         j.lzf_list[at++] = p;
@@ -1030,7 +1030,7 @@ DEV uint64_t note_fast(const DeviceJob& j, uint32_t base, uint64_t m, uint32_t r
 // it none, where its lanes had scanned all 277 K items)
 DEV void note_lane(const DeviceJob& j, uint32_t base, uint64_t m) {
     if (!m) return;
-    uint32_t at = atomicAdd(&j.counters[41], (uint32_t)__builtin_popcountll(m));
+    uint32_t at = atomicAdd(&j.counters[kCtrLaneCount], (uint32_t)__builtin_popcountll(m));
     for (; m; m &= m - 1) j.lane_list[at++] = base + (uint32_t)__builtin_ctzll(m);
 }
 // the blocks [0, (k & 63) + 1) of a group of 64
@@ -1039,7 +1039,7 @@ DEV uint64_t group_mask(uint32_t k) { return (k & 63) == 63 ? ~0ull : (1ull << (
 // i of m (lane 0): k_raw_copy copies them (BlockItem.fast = kLzfRaw)
 DEV void note_raw(const DeviceJob& j, uint32_t base, uint64_t m) {
     if (!m) return;
-    uint32_t at = atomicAdd(&j.counters[40], (uint32_t)__builtin_popcountll(m));
+    uint32_t at = atomicAdd(&j.counters[kCtrRawCount], (uint32_t)__builtin_popcountll(m));
     for (; m; m &= m - 1) {
         const uint32_t p = base + (uint32_t)__builtin_ctzll(m);
         j.raw_list[at++] = p;
@@ -1049,15 +1049,15 @@ DEV void note_raw(const DeviceJob& j, uint32_t base, uint64_t m) {
 
 // a long piece (walked by a wave in k_lz_walk): lane 0 appends it
 DEV void note_long(const DeviceJob& j, uint32_t idx) {
-    const uint32_t at = atomicAdd(&j.counters[11], 1u);
+    const uint32_t at = atomicAdd(&j.counters[kCtrLongCount], 1u);
     j.long_list[at] = idx;
-    const uint32_t aw = atomicAdd(&j.counters[38], 1u);
+    const uint32_t aw = atomicAdd(&j.counters[kCtrWlongCount], 1u);
     j.wlong_list[aw] = idx;
 }
 
 // reserve `nb` items (wave-uniform); UINT32_MAX when the list is full
 DEV uint32_t reserve_blocks(const DeviceJob& j, uint32_t nb) {
-    const uint32_t first = wave_fetch_add(&j.counters[4], nb);
+    const uint32_t first = wave_fetch_add(&j.counters[kCtrBlockCount], nb);
     return ((uint64_t)first + nb <= j.block_capacity) ? first : 0xFFFFFFFFu;
 }
 
@@ -1144,10 +1144,10 @@ DEV bool plan_lz4f(const DeviceJob& j, In& in, int64_t n, uint64_t src_abs, uint
         pos += 4 + bsz + (bcs ? 4 : 0);
     }
     if (linked) {
-        const uint32_t at = wave_fetch_add(&j.counters[7], 1u);
+        const uint32_t at = wave_fetch_add(&j.counters[kCtrLinkCount], 1u);
         if (lane() == 0) j.link_list[at] = item;
     }
-    fp.mode = 1;
+    fp.mode = kFrameLz4f;
     fp.first = first;
     fp.nb = nb;
     fp.ccs = ccs;
@@ -1214,7 +1214,7 @@ DEV bool plan_snappy_java(const DeviceJob& j, In& in, int64_t n, uint64_t src_ab
         plan += ulen;
         pos += clen;
     }
-    fp.mode = 2;
+    fp.mode = kFrameSnappy;
     fp.first = first;
     fp.nb = nb;
     fp.ccs = 0;
@@ -1243,7 +1243,7 @@ DEV bool plan_snappy_whole(const DeviceJob& j, int64_t n, uint64_t src_abs, uint
         note_long(j, first);
         note_lane(j, first, 1ull);
     }
-    fp.mode = 2;
+    fp.mode = kFrameSnappy;
     fp.first = first;
     fp.nb = 1;
     fp.ccs = 0;
@@ -1259,7 +1259,7 @@ DEV bool plan_snappy_whole(const DeviceJob& j, int64_t n, uint64_t src_abs, uint
 // whole on the sequential list.  Each item writes only its own plan.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_decode(DeviceJob j) {
-    const uint32_t count = j.counters[2];
+    const uint32_t count = j.counters[kCtrDecodeCount];
     const uint32_t nw = gridDim.x * (blockDim.x >> 6);
     for (uint32_t item = blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6); item < count; item += nw) {
         const uint32_t b = j.decode_list[item];
@@ -1271,11 +1271,12 @@ __global__ __launch_bounds__(256) void k_decode(DeviceJob j) {
         const uint64_t doff = uni64(j.dcap[b]);
         const uint64_t cap = uni64(j.dcap[b + 1]) - doff;
         FramePlan fp;
-        fp.mode = 0;
-        fp.first = fp.nb = fp.ccs = fp.ccs_val = fp.csf = fp.xxh = fp.pad = 0;
+        fp.mode = kFrameWhole;
+        fp.xxh = kXxhNotTaken;
+        fp.first = fp.nb = fp.ccs = fp.ccs_val = fp.csf = fp.pad = 0;
         fp.content_size = 0;
         if (doff + cap > j.decoded_capacity) {
-            fp.mode = 3;  // no room: DECODE_OVERFLOW
+            fp.mode = kFrameNoRoom;  // DECODE_OVERFLOW
         } else {
             In in;
             in_init(in, j.data + S, n);
@@ -1291,8 +1292,8 @@ __global__ __launch_bounds__(256) void k_decode(DeviceJob j) {
                 }
             }
             if (!planned) {
-                fp.mode = 0;
-                const uint32_t at = wave_fetch_add(&j.counters[6], 1u);
+                fp.mode = kFrameWhole;
+                const uint32_t at = wave_fetch_add(&j.counters[kCtrSeqCount], 1u);
                 if (lane() == 0) j.seq_list[at] = item;
             }
         }
@@ -1946,7 +1947,7 @@ struct SlabSink {
 // each: the wave stages 4 KiB of the stream at a time in LDS (16 bytes per
 // lane per load, one memory latency per window) and lane 0 walks it from
 // there, where a lane walking the stream in HBM waits a memory latency per
-// sequence.  Then one LANE per remaining piece, taken off counters[10]:
+// sequence.  Then one LANE per remaining piece, taken off counters[kCtrLaneCursor]:
 // block checksum, then the walk.  High occupancy: the lane walk is a chain
 // of dependent loads per lane.
 // ---------------------------------------------------------------------------
@@ -2105,7 +2106,7 @@ DEV void walk_snappy_long(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8*
         const uint32_t room = kSlabRecs - pos;
         uint32_t ns = 0xFFFFFFFFu, emit = cnt;
         if (cnt >= room) {
-            ns = wave_fetch_add(&j.counters[9], 1u);
+            ns = wave_fetch_add(&j.counters[kCtrSlabCursor], 1u);
             if (ns >= j.pool_slabs) {
                 emit = room;  // the pool ran out: the walk stops after the slab's last record
                 cut = true;
@@ -2303,7 +2304,7 @@ DEV void walk_lz4_wave(const DeviceJob& j, Piece& pc, SlabSink& sink, lds_u8* wi
         const uint32_t room = kSlabRecs - pos;
         uint32_t ns = 0xFFFFFFFFu, emit = cnt;
         if (cnt && cnt >= room) {
-            ns = wave_fetch_add(&j.counters[9], 1u);
+            ns = wave_fetch_add(&j.counters[kCtrSlabCursor], 1u);
             if (ns >= j.pool_slabs) {
                 emit = room;
                 cut = true;
@@ -2369,10 +2370,10 @@ DEV void walk_long(const DeviceJob& j, uint32_t p, lds_u8* win) {
     out.nrec = 0;
     out.first_slab = 0xFFFFFFFFu;
     if (pc.ps.st == 0) {
-        const uint32_t fs = wave_fetch_add(&j.counters[9], 1u);
+        const uint32_t fs = wave_fetch_add(&j.counters[kCtrSlabCursor], 1u);
         if (fs < j.pool_slabs) {
             out.first_slab = fs;
-            SlabSink sink{j.pool, j.slab_next, &j.counters[9], j.pool_slabs, fs, 0, 0, 0, {}, {}, {}};
+            SlabSink sink{j.pool, j.slab_next, &j.counters[kCtrSlabCursor], j.pool_slabs, fs, 0, 0, 0, {}, {}, {}};
             const int64_t n = pc.s.n;
             const bool lanes_store = (pc.kind & kBlkSnappy) != 0;  // records already stored by the lanes
             if (lanes_store) walk_snappy_long(j, pc, sink, win);
@@ -2452,16 +2453,16 @@ constexpr uint32_t kLaneWin = 256, kLaneSlot = kLaneWin + 16;  // + the spare by
 __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
     constexpr uint32_t kWaveLds = 64 * kLaneSlot > kWalkWin + 16 ? 64 * kLaneSlot : kWalkWin + 16;
     __shared__ __attribute__((aligned(16))) uint8_t wwin[4][kWaveLds];
-    const uint32_t reserved = j.counters[4];
+    const uint32_t reserved = j.counters[kCtrBlockCount];
     const uint32_t nblk = reserved < j.block_capacity ? reserved : j.block_capacity;
-    const uint32_t nlong = j.counters[38];
-    const uint32_t nlane = j.counters[41] < j.block_capacity ? j.counters[41] : j.block_capacity;
+    const uint32_t nlong = j.counters[kCtrWlongCount];
+    const uint32_t nlane = j.counters[kCtrLaneCount] < j.block_capacity ? j.counters[kCtrLaneCount] : j.block_capacity;
     // few pieces: fewer than 512 per CU (the grid is 16 workgroups per CU, 2
     // resident: 512 lanes)
     const bool few = nblk < gridDim.x * 32u;
     lds_u8* wl = (lds_u8*)wwin[threadIdx.x >> 6];
     for (;;) {
-        const uint32_t k = wave_fetch_add(&j.counters[39], 1u);
+        const uint32_t k = wave_fetch_add(&j.counters[kCtrWlongCursor], 1u);
         if (k >= nlong) break;
         const uint32_t p = uni32(j.wlong_list[k]);
         if (uni32(j.blocks[p].fast) != kLzfNone) continue;  // the fast path has it
@@ -2473,7 +2474,7 @@ __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
     bool active = false, drained = false;
     uint32_t p = 0, first_slab = 0;
     Piece pc;
-    SlabSink sink{j.pool, j.slab_next, &j.counters[9], j.pool_slabs, 0, 0, 0, 0, {}, {}, {}};
+    SlabSink sink{j.pool, j.slab_next, &j.counters[kCtrSlabCursor], j.pool_slabs, 0, 0, 0, 0, {}, {}, {}};
     for (;;) {
         // lanes without a piece take the next ones, one claim per wave (a
         // claim per lane serialised ~277K atomics on C2: 1.5 ms); pieces that
@@ -2485,7 +2486,7 @@ __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
             if (!wm) break;
             const int lead = __builtin_ctzll(wm);
             uint32_t u0 = 0;
-            if (lane() == (uint32_t)lead) u0 = atomicAdd(&j.counters[10], (uint32_t)__builtin_popcountll(wm));
+            if (lane() == (uint32_t)lead) u0 = atomicAdd(&j.counters[kCtrLaneCursor], (uint32_t)__builtin_popcountll(wm));
             const uint32_t u = rl(u0, lead) + (uint32_t)__builtin_popcountll(wm & ((1ull << lane()) - 1));
             if (!want) continue;
             if (u >= nlane) {
@@ -2499,7 +2500,7 @@ __global__ __launch_bounds__(256) void k_lz_walk(DeviceJob j) {
             piece_begin(pc, j, it);
             first_slab = 0xFFFFFFFFu;
             if (pc.ps.st == 0) {
-                const uint32_t fs = atomicAdd(&j.counters[9], 1u);
+                const uint32_t fs = atomicAdd(&j.counters[kCtrSlabCursor], 1u);
                 if (fs < j.pool_slabs) {
                     first_slab = fs;
                     sink.slab = fs;
@@ -2700,7 +2701,7 @@ DEV void exec_chunk(const DeviceJob& j, lds_u8* ring, SeqRec* buf, uint32_t base
 // ---------------------------------------------------------------------------
 // k_lz_exec: persistent, kExecWaves independent waves per workgroup (a
 // 16 KiB LDS ring each), one workgroup per CU; units by one agent-scope
-// counter (counters[8]):
+// counter (counters[kCtrExecCursor]):
 // first the linked frames, then the long pieces one unit each (a 1 MiB raw
 // snappy payload is ~1000 record batches: taken first, and alone, it no
 // longer ends the kernel behind 63 other pieces of its chunk), then the
@@ -2722,13 +2723,13 @@ __global__ __launch_bounds__(64 * kExecWaves) void k_lz_exec(DeviceJob j) {
     const __attribute__((address_space(3))) uint32_t* pat = (const __attribute__((address_space(3))) uint32_t*)pat_w;
     lds_cu32* ct = (lds_cu32*)ct_w;
     SeqRec* buf = j.seqs + ((size_t)blockIdx.x * kExecWaves + wi) * kRecsPerLane;
-    const uint32_t nlink = j.counters[7];
-    const uint32_t reserved = j.counters[4];
+    const uint32_t nlink = j.counters[kCtrLinkCount];
+    const uint32_t reserved = j.counters[kCtrBlockCount];
     const uint32_t nblk = reserved < j.block_capacity ? reserved : j.block_capacity;
-    const uint32_t nlong = j.counters[11];
+    const uint32_t nlong = j.counters[kCtrLongCount];
     const uint32_t total = nlink + nlong + (nblk + 63) / 64;
     for (;;) {
-        const uint32_t u = wave_fetch_add(&j.counters[8], 1u);
+        const uint32_t u = wave_fetch_add(&j.counters[kCtrExecCursor], 1u);
         if (u >= total) break;
         if (u < nlink) {
             exec_linked(j, ring, buf, uni32(j.link_list[u]), pat, ct);
@@ -2760,7 +2761,7 @@ __global__ __launch_bounds__(kRawThreads) void k_raw_copy(DeviceJob j) {
     }
     __syncthreads();
     lds_cu32* ct = (lds_cu32*)ct_w;
-    const uint32_t nraw = j.counters[40];
+    const uint32_t nraw = j.counters[kCtrRawCount];
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
     for (uint32_t u = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); u < nraw; u += waves) {
         const uint32_t p = uni32(j.raw_list[u]);
@@ -2773,7 +2774,7 @@ __global__ __launch_bounds__(kRawThreads) void k_raw_copy(DeviceJob j) {
         if (lane() == 0) {
             j.blocks[p].out = (int32_t)n;
             j.blocks[p].crc = pcrc;
-            atomicAdd((unsigned long long*)(j.counters + 24), (unsigned long long)n);  // k_crc_compose's gate
+            atomicAdd((unsigned long long*)(j.counters + kCtrRawBytes64), (unsigned long long)n);  // k_crc_compose's gate
         }
     }
 }
@@ -2800,9 +2801,9 @@ __global__ __launch_bounds__(64 * kExecWaves) void k_zexec(DeviceJob j) {
     __syncthreads();
     const __attribute__((address_space(3))) uint32_t* pat = (const __attribute__((address_space(3))) uint32_t*)pat_w;
     lds_cu32* ct = (lds_cu32*)ct_w;
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[21], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrZexecCursor], 1u);
         if (i >= count) break;
         if (uni32(j.inf_state[i]) != kZsFast) continue;
         const uint32_t b = uni32(j.inf_list[i]);
@@ -2835,13 +2836,13 @@ __global__ __launch_bounds__(64 * kExecWaves) void k_zexec(DeviceJob j) {
 // k_decode_blocks: the sequential frames (what the planner did not split:
 // truncated or malformed frames, linked frames of more than 64 blocks,
 // unplannable snappy-java streams), one per lane through the lane engine,
-// taken off counters[5].
+// taken off counters[kCtrSeqCursor].
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_decode_blocks(DeviceJob j) {
-    const uint32_t nseq = j.counters[6];
+    const uint32_t nseq = j.counters[kCtrSeqCount];
     const int64_t data_len = (int64_t)j.data_len;
     for (;;) {
-        const uint32_t item = atomicAdd(&j.counters[5], 1u);
+        const uint32_t item = atomicAdd(&j.counters[kCtrSeqCursor], 1u);
         if (item >= nseq) break;
         const uint32_t b = j.decode_list[j.seq_list[item]];
         rpgpu_batch_result* R = &j.batches[b];
@@ -2871,28 +2872,28 @@ __global__ __launch_bounds__(256) void k_decode_blocks(DeviceJob j) {
 __global__ __launch_bounds__(256) void k_decode_finish(DeviceJob j, int defer) {
     __shared__ __attribute__((aligned(16))) uint8_t xb[4][1024];
     lds_u8* xbuf = (lds_u8*)xb[threadIdx.x >> 6];
-    const uint32_t count = j.counters[2];
+    const uint32_t count = j.counters[kCtrDecodeCount];
     const uint32_t l = lane();
     // frames claimed one at a time: the content checksums are long serial
     // chains (~1 ms per MiB: XXH32's four accumulators, one lane each) and
-    // only some frames carry one, so those are claimed first (counters[44])
-    // and all start at once; the rest after them (counters[14]).  (In item
+    // only some frames carry one, so those are claimed first (kCtrXxhCursor)
+    // and all start at once; the rest after them (kCtrFinishCursor).  (In item
     // order a wave could meet two 1 MiB checksummed frames in a row: C2's
     // k_decode_finish 2.5-3.1 ms.)
     for (uint32_t phase = defer ? 1u : 0u; phase < 2; phase++)
     for (;;) {
-        const uint32_t item = wave_fetch_add(&j.counters[phase == 0 ? 44 : 14], 1u);
+        const uint32_t item = wave_fetch_add(&j.counters[phase == 0 ? kCtrXxhCursor : kCtrFinishCursor], 1u);
         if (item >= count) break;
         const uint32_t mode = uni32(j.plans[item].mode);
-        const bool xxh_first = mode == 1 && uni32(j.plans[item].ccs) != 0;
+        const bool xxh_first = mode == kFrameLz4f && uni32(j.plans[item].ccs) != 0;
         if (!defer && xxh_first != (phase == 0)) continue;
         const uint32_t b = uni32(j.decode_list[item]);
         rpgpu_batch_result* R = &j.batches[b];
-        if (mode == 3) {
+        if (mode == kFrameNoRoom) {
             if (l == 0) R->flags = R->flags | RPGPU_F_DECODE_OVERFLOW;
             continue;
         }
-        if (mode == 0) continue;
+        if (mode == kFrameWhole) continue;
         const uint32_t first = uni32(j.plans[item].first), nb = uni32(j.plans[item].nb);
         const uint64_t d0 = uni64(j.dcap[b]);
         bool ok = true, moved = false;
@@ -2921,7 +2922,7 @@ __global__ __launch_bounds__(256) void k_decode_finish(DeviceJob j, int defer) {
             run += (uint64_t)out;
         }
         const uint64_t total = run - d0;
-        if (ok && mode == 1) {
+        if (ok && mode == kFrameLz4f) {
             if (uni32(j.plans[item].csf) && total != uni64(j.plans[item].content_size)) ok = false;  // frameSize_wrong
             if (ok && !(defer && !moved) && uni32(j.plans[item].ccs) &&
                 xxh32_wave(j.decoded + d0, total, 0, xbuf) != uni32(j.plans[item].ccs_val))
@@ -2974,16 +2975,16 @@ constexpr int kXxhPrio = 1;
 __global__ __launch_bounds__(256) void k_content_xxh(DeviceJob j) {
     __shared__ __attribute__((aligned(16))) uint8_t xb[4][1024];
     lds_u8* xbuf = (lds_u8*)xb[threadIdx.x >> 6];
-    const uint32_t count = j.counters[2];
+    const uint32_t count = j.counters[kCtrDecodeCount];
     const uint32_t l = lane();
     // first in issue on a shared SIMD (k_dchain, which waits on memory, is
     // above it): beside k_decode_finish's waves at equal priority the chains
     // ran ~1.4x their time alone
     __builtin_amdgcn_s_setprio(kXxhPrio);
     for (;;) {
-        const uint32_t item = wave_fetch_add(&j.counters[44], 1u);
+        const uint32_t item = wave_fetch_add(&j.counters[kCtrXxhCursor], 1u);
         if (item >= count) break;
-        if (uni32(j.plans[item].mode) != 1u || uni32(j.plans[item].ccs) == 0u) continue;
+        if (uni32(j.plans[item].mode) != kFrameLz4f || !uni32(j.plans[item].ccs)) continue;
         const uint32_t b = uni32(j.decode_list[item]);
         const uint32_t first = uni32(j.plans[item].first), nb = uni32(j.plans[item].nb);
         const uint64_t d0 = uni64(j.dcap[b]);
@@ -2999,7 +3000,8 @@ __global__ __launch_bounds__(256) void k_content_xxh(DeviceJob j) {
         }
         if (wave_or(bad)) continue;  // moved (or failed): k_decode_finish's
         if (uni32(j.plans[item].csf) && carry != uni64(j.plans[item].content_size)) continue;  // fails there
-        const uint32_t v = xxh32_wave(j.decoded + d0, carry, 0, xbuf) == uni32(j.plans[item].ccs_val) ? 1u : 2u;
+        const bool match = xxh32_wave(j.decoded + d0, carry, 0, xbuf) == uni32(j.plans[item].ccs_val);
+        const uint32_t v = match ? kXxhMatch : kXxhMismatch;
         if (l == 0) j.plans[item].xxh = v;
     }
 }
@@ -3010,9 +3012,9 @@ __global__ __launch_bounds__(256) void k_content_xxh(DeviceJob j) {
 // (k_dchain may have chained the frame's payload meanwhile: never read, its
 // verdict now fails dchain_ok.)
 __global__ __launch_bounds__(256) void k_content_apply(DeviceJob j) {
-    const uint32_t count = j.counters[2];
+    const uint32_t count = j.counters[kCtrDecodeCount];
     for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < count; item += gridDim.x * blockDim.x) {
-        if (j.plans[item].xxh != 2u) continue;
+        if (j.plans[item].xxh != kXxhMismatch) continue;
         rpgpu_batch_result* R = &j.batches[j.decode_list[item]];
         R->flags = R->flags & ~(uint32_t)RPGPU_F_CODEC_OK;
         R->decoded_len = 0;
@@ -3194,7 +3196,7 @@ static_assert(kFLaneWgs >= 1, "lane windows");
 __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
     __shared__ __attribute__((aligned(16))) uint8_t fwin[256 * kFSlot];
     lds_u8* slot = (lds_u8*)fwin + kFSlot * threadIdx.x;
-    const uint32_t cnt_list = j.counters[45];
+    const uint32_t cnt_list = j.counters[kCtrLzfCount];
     const uint32_t nlist = cnt_list < j.block_capacity ? cnt_list : j.block_capacity;
     bool active = false, drained = false;
     uint32_t p = 0, n = 0, cap = 0, ip = 0, op = 0, r = 0, resv = 0, base = 0;
@@ -3210,7 +3212,7 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
             if (!wm) break;
             const int lead = __builtin_ctzll(wm);
             uint32_t u0 = 0;
-            if (lane() == (uint32_t)lead) u0 = atomicAdd(&j.counters[46], (uint32_t)__builtin_popcountll(wm));
+            if (lane() == (uint32_t)lead) u0 = atomicAdd(&j.counters[kCtrLzfCursor], (uint32_t)__builtin_popcountll(wm));
             const uint32_t u = rl(u0, lead) + (uint32_t)__builtin_popcountll(wm & ((1ull << lane()) - 1));
             if (!want) continue;
             if (u >= nlist) {
@@ -3283,7 +3285,7 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
         }
         if (active && outcome == 1) {
             // the rest is the reference loop's: k_lzf_tail
-            const uint32_t t = atomicAdd(&j.counters[47], 1u);
+            const uint32_t t = atomicAdd(&j.counters[kCtrLzfTailCount], 1u);
             j.lzf_tail[t] = p;
             PieceState ps;
             ps.ip = (int32_t)ip;
@@ -3313,7 +3315,7 @@ __global__ __launch_bounds__(256) void k_lzf_walk(DeviceJob j) {
 // ordinary one (the reference's fast loop, every earlier sequence having been
 // one) to the block's end, one lane per block
 __global__ __launch_bounds__(256) void k_lzf_tail(DeviceJob j) {
-    const uint32_t nt = j.counters[47];
+    const uint32_t nt = j.counters[kCtrLzfTailCount];
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += gridDim.x * blockDim.x) {
         const uint32_t p = j.lzf_tail[t];
         const BlockItem it = j.blocks[p];

@@ -168,7 +168,7 @@ DEV void key_insert(const CompactArgs& a, uint32_t slot, const uint8_t* k, uint3
             __hip_atomic_fetch_max(&a.table[idx], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
-        if (!WAVE || lane() == 0) atomicAdd(&a.counters[0], 1u);
+        if (!WAVE || lane() == 0) atomicAdd(&a.counters[kCcKeyMismatches], 1u);
     }
 }
 
@@ -473,8 +473,8 @@ __global__ __launch_bounds__(256) void k_cplan(CompactArgs a) {
         T->out_batch_capacity_needed = nout;
         const uint32_t ov = (bytes + 16 > a.job.out_capacity ? 1u : 0u) | (nout > a.job.out_batch_capacity ? 2u : 0u);
         T->overflow = ov;
-        T->key_compare_mismatches = a.counters[0];
-        a.counters[1] = ov ? 0u : (uint32_t)nout;
+        T->key_compare_mismatches = a.counters[kCcKeyMismatches];
+        a.counters[kCcStampCount] = ov ? 0u : (uint32_t)nout;
         a.job.d_out_seg_offsets[a.job.n_segments] = bytes;
     }
     if (s >= a.job.n_segments) return;

@@ -743,7 +743,7 @@ done:
 
 // ---------------------------------------------------------------------------
 // Job passes.  k_emit lists the gzip and zstd batches of RPGPU_JOB_DECODE
-// jobs (inf_list, counters[16] items).
+// jobs (inf_list, counters[kCtrInfCount] items).
 //   first pass (k_members_first, after k_emit, before the slot scans): one
 //     wave per member decodes it into a scratch slot of the context's pool,
 //     sized from the member's ISIZE trailer (gzip, capped by deflate's 1032:1
@@ -751,11 +751,11 @@ done:
 //     reservation (dcap: the output rounded up to 16, 0 when the stream is
 //     rejected, the plan rule of the reference's sizing pass: for gzip a
 //     failed data / length check still reserves) and index slots, and its
-//     state: 0 decoded and checked (the bytes wait in scratch), 1 rejected,
-//     2 the output outgrew the scratch slot (or the pool ran out): decoded
-//     again by the second pass;
-//   k_inflate_copy: state 0 members from scratch into their arena slots;
-//   second pass (k_members): state 2 members, into the slot.
+//     state (InfState): kInfDecoded decoded and checked (the bytes wait in
+//     scratch), kInfRejected, kInfAgain the output outgrew the scratch slot
+//     (or the pool ran out): decoded again by the second pass;
+//   k_inflate_copy: kInfDecoded members from scratch into their arena slots;
+//   second pass (k_members): kInfAgain members, into the slot.
 // The reference decodes every gzip payload twice (buffer_for_input, then the
 // real pass); here a well-formed member is decoded once.
 // k_validate_decoded then computes the new crc / header_crc and walks it.
@@ -844,7 +844,7 @@ DEV void gzip_first_item(const DeviceJob& j, uint8_t* lds, InfTabs* T, const Inf
         const int32_t rcount = R->record_count;
         j.dcap[b] = cap;
         j.slots[b] = ((j.flags & RPGPU_JOB_PARSE) && rcount > 0 && (uint64_t)rcount <= cap) ? (uint64_t)rcount : 0;
-        j.inf_state[i] = rc != 0 ? 1u : over ? 2u : 0u;
+        j.inf_state[i] = rc != 0 ? kInfRejected : over ? kInfAgain : kInfDecoded;
         j.inf_off[i] = soff;
         j.inf_total[i] = total;
     }
@@ -852,10 +852,10 @@ DEV void gzip_first_item(const DeviceJob& j, uint8_t* lds, InfTabs* T, const Inf
 
 // decoded members from scratch into their arena slots (one wave per member)
 __global__ __launch_bounds__(256) void k_inflate_copy(DeviceJob j) {
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     const uint32_t l = lane();
     for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < count; i += gridDim.x * 4) {
-        if (uni32(j.inf_state[i]) != 0) continue;
+        if (uni32(j.inf_state[i]) != kInfDecoded) continue;
         const uint32_t b = uni32(j.inf_list[i]);
         rpgpu_batch_result* R = &j.batches[b];
         const uint64_t dst = uni64(j.dcap[b]), cap = uni64(j.dcap[b + 1]) - dst, total = uni64(j.inf_total[i]);
@@ -2328,7 +2328,7 @@ DEV void zs_plan_items(ZLane& e, zs::Tabs* T, const DeviceJob& j, uint64_t src_o
 }
 
 // the fast path of zstd member i: 0 not taken (the wave decoder runs), else
-// the state set (1 rejected, kZsFast parsed)
+// the state set (kInfRejected, kZsFast parsed)
 DEV uint32_t zstd_fast_item(const DeviceJob& j, uint8_t* lds, uint32_t i, uint32_t b, const rpgpu_batch_result* R) {
     // k_zplan sized the member's buffers (ZsFastDesc at inf_off[i]) and
     // k_zlits decoded its Huffman literal blocks ahead
@@ -2376,11 +2376,11 @@ DEV uint32_t zstd_fast_item(const DeviceJob& j, uint8_t* lds, uint32_t i, uint32
         if (lane() == 0) {
             j.dcap[b] = 0;
             j.slots[b] = 0;
-            j.inf_state[i] = 1;
+            j.inf_state[i] = kInfRejected;
             j.inf_off[i] = 0;
             j.inf_total[i] = 0;
         }
-        return 1;
+        return kInfRejected;
     }
     if (e.pend) e.match(0, 0);  // the literals after the last match
     if (unsure || e.bad || e.nlit + e.mlsum != total || total >= (1ull << 31)) return 0;
@@ -2431,8 +2431,8 @@ DEV void zstd_first_item(const DeviceJob& j, uint8_t* lds, uint32_t i, uint32_t 
         const int32_t rcount = R->record_count;
         j.dcap[b] = cap;
         j.slots[b] = ((j.flags & RPGPU_JOB_PARSE) && rcount > 0 && (uint64_t)rcount <= cap) ? (uint64_t)rcount : 0;
-        j.inf_state[i] = dirty ? kZsExact : rc != 0 ? 1u : again ? 2u : 0u;
-        if (dirty) atomicAdd(&j.counters[27], 1u);
+        j.inf_state[i] = dirty ? kZsExact : rc != 0 ? kInfRejected : again ? kInfAgain : kInfDecoded;
+        if (dirty) atomicAdd(&j.counters[kCtrZexactCount], 1u);
         j.inf_off[i] = soff;
         j.inf_total[i] = total;
     }
@@ -2754,13 +2754,13 @@ struct zs::ExactRing<ZExact> {
 
 // k_zexact: pass 0 (after the first pass, before the slot scans) decodes the
 // kZsExact members into scratch slots and sets their plan and state as
-// zstd_first_item does (kZsExactAgain instead of 2); pass 1 (after
+// zstd_first_item does (kZsExactAgain instead of kInfAgain); pass 1 (after
 // k_members) decodes the kZsExactAgain ones into their arena slots.  One
 // wave, lane 0; the buffer and the literal buffer from the scratch pool.
 __global__ __launch_bounds__(64) void k_zexact(DeviceJob j, int pass) {
     extern __shared__ __attribute__((aligned(16))) uint8_t zlds[];
-    if (threadIdx.x != 0 || !j.inf_scratch || j.counters[27] == 0) return;
-    const uint32_t count = j.counters[16];
+    if (threadIdx.x != 0 || !j.inf_scratch || j.counters[kCtrZexactCount] == 0) return;
+    const uint32_t count = j.counters[kCtrInfCount];
     zs::Tabs* T = (zs::Tabs*)zlds;
     uint8_t* work = nullptr;
     for (uint32_t i = 0; i < count; i++) {
@@ -2771,13 +2771,13 @@ __global__ __launch_bounds__(64) void k_zexact(DeviceJob j, int pass) {
         const uint64_t S = j.seg_off[R->segment] + R->file_pos + RPGPU_HEADER_SIZE;
         const uint64_t n = (uint64_t)(uint32_t)(R->size_bytes - (int32_t)RPGPU_HEADER_SIZE);
         // the buffers: taken from the pool by the first pass, kept for the
-        // second ([31]: offset / 16 + 1, 0 while none)
-        if (!work && j.counters[31]) work = j.inf_scratch + 16ull * (j.counters[31] - 1);
+        // second (kCtrZexactWork: offset / 16 + 1, 0 while none)
+        if (!work && j.counters[kCtrZexactWork]) work = j.inf_scratch + 16ull * (j.counters[kCtrZexactWork] - 1);
         if (!work && pass == 0) {
             const uint64_t w = atomicAdd((unsigned long long*)j.inf_scratch_used, (unsigned long long)(kZxBuf + kZxBlk));
             if (w + kZxBuf + kZxBlk <= j.inf_scratch_bytes) {
                 work = j.inf_scratch + w;
-                j.counters[31] = (uint32_t)(w >> 4) + 1;
+                j.counters[kCtrZexactWork] = (uint32_t)(w >> 4) + 1;
             }
         }
         ZExact e;
@@ -2820,7 +2820,7 @@ __global__ __launch_bounds__(64) void k_zexact(DeviceJob j, int pass) {
             const int32_t rcount = R->record_count;
             j.dcap[b] = dcap;
             j.slots[b] = ((j.flags & RPGPU_JOB_PARSE) && rcount > 0 && (uint64_t)rcount <= dcap) ? (uint64_t)rcount : 0;
-            j.inf_state[i] = rc != 0 ? 1u : again ? kZsExactAgain : 0u;
+            j.inf_state[i] = rc != 0 ? kInfRejected : again ? kZsExactAgain : kInfDecoded;
             j.inf_off[i] = soff;
             j.inf_total[i] = total;
         } else if (rc == 0 && !unsure && !e.over) {
@@ -2838,8 +2838,8 @@ __global__ __launch_bounds__(64) void k_zexact(DeviceJob j, int pass) {
 // by side.  The gzip CRC table shares LDS with the zstd tables: it is
 // reloaded before a gzip member that follows a zstd one.
 //   k_members_first (after k_emit, before the slot scans): the first pass;
-//   k_inflate_copy: state-0 members from scratch into the arena;
-//   k_members: the second pass of state-2 members.
+//   k_inflate_copy: kInfDecoded members from scratch into the arena;
+//   k_members: the second pass of kInfAgain members.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kMemLds = kZsLds > kInfLdsDecode ? kZsLds : kInfLdsDecode;
 
@@ -2852,12 +2852,14 @@ __global__ __launch_bounds__(64) void k_members_first(DeviceJob j, int pass) {
     InfTabs* T = (InfTabs*)(lds + kInfRing);
     const InfWave W = inf_wave();
     bool tab = false;
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     // largest first (a member decodes serially, so a big one claimed last
     // would set the pass's tail): members of >= 128 KiB stored, then the rest
     for (uint32_t phase = 0; phase < 2; phase++) {
+        const JobCounter cursor = pass == 2 ? (phase ? kCtrMembersFirstP2Cursor2 : kCtrMembersFirstP2Cursor)
+                                            : (phase ? kCtrMembersFirstCursor2 : kCtrMembersFirstCursor);
         for (;;) {
-            const uint32_t i = wave_fetch_add(&j.counters[pass == 2 ? (phase ? 49 : 48) : (phase ? 20 : 17)], 1u);
+            const uint32_t i = wave_fetch_add(&j.counters[cursor], 1u);
             if (i >= count) break;
             const uint32_t b = uni32(j.inf_list[i]);
             const rpgpu_batch_result* R = &j.batches[b];
@@ -2885,7 +2887,6 @@ __global__ __launch_bounds__(64) void k_members_first(DeviceJob j, int pass) {
 // take kZsPending; k_zfallback (after the join, before the slot scans) runs
 // the wave decoder on those.  (Separate kernels: the lane parser's VGPR state
 // and the wave decoder's SGPR state in one register allocation spilled.)
-constexpr uint32_t kZsPending = 4;
 
 // k_zplan: per zstd member, zs_fast_size's header walk, the scratch region
 // (descriptor, literal buffer, records, literal and sequence items, table
@@ -2894,10 +2895,10 @@ constexpr uint32_t kZsPending = 4;
 // kZsPending for the wave decoder
 __global__ __launch_bounds__(64) void k_zplan(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     zs::Tabs* T = (zs::Tabs*)(lds + kInfRing);
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[30], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrZplanCursor], 1u);
         if (i >= count) break;
         const uint32_t b = uni32(j.inf_list[i]);
         const rpgpu_batch_result* R = &j.batches[b];
@@ -2937,7 +2938,7 @@ __global__ __launch_bounds__(64) void k_zplan(DeviceJob j) {
                 P.tabs_off = soff + o_tab;
                 P.seqs_off = soff + o_seq;
                 zs_plan_items(e, T, j, S, soff, P);
-                const uint32_t first = wave_fetch_add(&j.counters[28], P.nl + P.ns);
+                const uint32_t first = wave_fetch_add(&j.counters[kCtrZsItemCount], P.nl + P.ns);
                 if (lane() == 0) {
                     for (uint32_t k = 0; k < P.nl && first + k < j.zs_items_cap; k++)
                         j.zs_items[first + k] = soff + o_li + (uint64_t)k * sizeof(ZsLitItem);
@@ -3069,11 +3070,11 @@ DEV void zseq_item(const DeviceJob& j, zs::Tabs* T, ZsSeqItem* it, inf_lds_u8* w
 __global__ __launch_bounds__(64) void k_zlits(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     zs::Tabs* T = (zs::Tabs*)lds;  // the tables only (no ring): kZsTabBytes of LDS, more waves per CU
-    const uint32_t reg = j.counters[28];
+    const uint32_t reg = j.counters[kCtrZsItemCount];
     const uint32_t count = reg < j.zs_items_cap ? reg : j.zs_items_cap;
     const uint32_t l = lane();
     for (;;) {
-        const uint32_t k = wave_fetch_add(&j.counters[29], 1u);
+        const uint32_t k = wave_fetch_add(&j.counters[kCtrZlitsCursor], 1u);
         if (k >= count) break;
         const uint64_t ref = uni64(j.zs_items[k]);
         if (ref >> 63) {
@@ -3115,10 +3116,10 @@ __global__ __launch_bounds__(64) void k_zlits(DeviceJob j) {
 
 __global__ __launch_bounds__(64) void k_zparse(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     for (uint32_t phase = 0; phase < 2; phase++) {
         for (;;) {
-            const uint32_t i = wave_fetch_add(&j.counters[phase ? 23 : 22], 1u);
+            const uint32_t i = wave_fetch_add(&j.counters[phase ? kCtrZparseCursor2 : kCtrZparseCursor], 1u);
             if (i >= count) break;
             if (uni32(j.inf_state[i]) != kZsPlanned) continue;
             const uint32_t b = uni32(j.inf_list[i]);
@@ -3132,9 +3133,9 @@ __global__ __launch_bounds__(64) void k_zparse(DeviceJob j) {
 
 __global__ __launch_bounds__(64) void k_zfallback(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[26], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrZfallbackCursor], 1u);
         if (i >= count) break;
         const uint32_t b = uni32(j.inf_list[i]);
         const rpgpu_batch_result* R = &j.batches[b];
@@ -3149,11 +3150,11 @@ __global__ __launch_bounds__(64) void k_members(DeviceJob j) {
     InfTabs* T = (InfTabs*)(lds + kInfRing);
     const InfWave W = inf_wave();
     bool tab = false;
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[18], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrMembersCursor], 1u);
         if (i >= count) break;
-        if (uni32(j.inf_state[i]) != 2) continue;
+        if (uni32(j.inf_state[i]) != kInfAgain) continue;
         const uint32_t b = uni32(j.inf_list[i]);
         rpgpu_batch_result* R = &j.batches[b];
         const uint64_t dst = uni64(j.dcap[b]), cap = uni64(j.dcap[b + 1]) - dst;
@@ -3205,7 +3206,7 @@ DEV void gzs_null(DeviceJob& j, uint32_t from, uint32_t to) {
 
 // one thread per member: the gzip header, the chunks
 __global__ __launch_bounds__(256) void k_gzsplan(DeviceJob j) {
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     j.gzs_mem[2 * i] = 0;
@@ -3233,7 +3234,7 @@ __global__ __launch_bounds__(256) void k_gzsplan(DeviceJob j) {
     uint32_t nk = (uint32_t)((nd + kGzsChunk - 1) / kGzsChunk);
     nk = nk < kGzsMaxK ? nk : kGzsMaxK;
     const uint64_t csz = (nd + nk - 1) / nk;
-    const uint32_t base = atomicAdd(&j.counters[32], nk);
+    const uint32_t base = atomicAdd(&j.counters[kCtrGzsItemCount], nk);
     if ((uint64_t)base + nk > j.gzs_items_cap) {
         gzs_null(j, base, base + nk);
         return;
@@ -3264,9 +3265,9 @@ __global__ __launch_bounds__(64) void k_gzsfind(DeviceJob j) {
     const uint32_t l = lane();
     inf_lds_u8* tb = (inf_lds_u8*)lds + 128 * l;
     gzs_lds_u32* w = (gzs_lds_u32*)(lds + 64 * 128);
-    const uint32_t nit = min(j.counters[32], j.gzs_items_cap);
+    const uint32_t nit = min(j.counters[kCtrGzsItemCount], j.gzs_items_cap);
     for (;;) {
-        const uint32_t t = wave_fetch_add(&j.counters[33], 1u);
+        const uint32_t t = wave_fetch_add(&j.counters[kCtrGzsFindCursor], 1u);
         if (t >= nit) break;
         GzsItem* it = &j.gzs_items[t];
         if (uni32(it->member) == ~0u || uni32(it->k) == 0) continue;
@@ -3357,10 +3358,10 @@ __global__ __launch_bounds__(64) void k_gzsdecode(DeviceJob j) {
     gzs_lds_u16* ring = (gzs_lds_u16*)lds;
     InfTabs* T = (InfTabs*)(lds + 2 * kGzsRing);
     const InfSymTabs ST = inf_sym_tabs();
-    const uint32_t nit = min(j.counters[32], j.gzs_items_cap);
-    unsigned long long* used = (unsigned long long*)(j.counters + 36);
+    const uint32_t nit = min(j.counters[kCtrGzsItemCount], j.gzs_items_cap);
+    unsigned long long* used = (unsigned long long*)(j.counters + kCtrGzsPoolUsed64);
     for (;;) {
-        const uint32_t t = wave_fetch_add(&j.counters[34], 1u);
+        const uint32_t t = wave_fetch_add(&j.counters[kCtrGzsDecodeCursor], 1u);
         if (t >= nit) break;
         GzsItem* it = &j.gzs_items[t];
         if (uni32(it->member) == ~0u) continue;
@@ -3427,10 +3428,10 @@ __global__ __launch_bounds__(256) void k_gzsresolve(DeviceJob j) {
         for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
         tab[tid] = c;
     }
-    const uint32_t count = j.counters[16];
+    const uint32_t count = j.counters[kCtrInfCount];
     for (;;) {
         __syncthreads();
-        if (tid == 0) s_i = atomicAdd(&j.counters[35], 1u);
+        if (tid == 0) s_i = atomicAdd(&j.counters[kCtrGzsResolveCursor], 1u);
         __syncthreads();
         const uint32_t i = s_i;
         if (i >= count) break;
@@ -3545,7 +3546,7 @@ __global__ __launch_bounds__(256) void k_gzsresolve(DeviceJob j) {
             const int32_t rcount = R->record_count;
             j.dcap[b] = cap;
             j.slots[b] = ((j.flags & RPGPU_JOB_PARSE) && rcount > 0 && (uint64_t)rcount <= cap) ? (uint64_t)rcount : 0;
-            j.inf_state[i] = rc != 0 ? 1u : 0u;
+            j.inf_state[i] = rc != 0 ? kInfRejected : kInfDecoded;
             j.inf_off[i] = rc == 1 ? 0 : s_soff;
             j.inf_total[i] = rc == 1 ? 0 : total;
             j.gzs_mem[2 * i + 1] = nk | (1u << 31);

@@ -120,23 +120,48 @@ struct PieceState {
     uint32_t first_slab;        // 0xFFFFFFFF: none
 };
 
+// FramePlan::mode
+enum FrameMode : uint32_t {
+    kFrameWhole = 0,   // decoded whole by k_decode_blocks (seq_list: what the planner did not split)
+    kFrameLz4f = 1,    // LZ4F blocks
+    kFrameSnappy = 2,  // snappy-java chunks, or a raw snappy stream as one piece
+    kFrameNoRoom = 3,  // no arena room: DECODE_OVERFLOW
+};
+// FramePlan::xxh
+enum FrameXxh : uint32_t {
+    kXxhNotTaken = 0,  // k_content_xxh left the frame to k_decode_finish
+    kXxhMatch = 1,
+    kXxhMismatch = 2,  // k_content_apply takes the frame's verdict back
+};
 // Per decode item: how its payload is being decoded
 struct FramePlan {
-    uint32_t mode;   // 0 decoded whole by one wave, 1 LZ4F blocks, 2 snappy-java chunks, 3 no arena room
+    uint32_t mode;   // FrameMode
     uint32_t first;  // first BlockItem
     uint32_t nb;     // number of BlockItems
     uint32_t ccs;    // LZ4F: content checksum present
     uint64_t content_size;  // LZ4F: content size (0 = absent)
     uint32_t ccs_val;       // LZ4F: stored content checksum
     uint32_t csf;           // LZ4F: content size present
-    uint32_t xxh;           // k_content_xxh's verdict: 0 not taken, 1 match, 2 mismatch
+    uint32_t xxh;           // k_content_xxh's verdict (FrameXxh)
     uint32_t pad;
 };
 
-// zstd members parsed into records (rp_inflate.hip zstd_fast_item): inf_state
-// kZsFast, inf_off -> a ZsFastDesc in the scratch pool; k_zexec (rp_codec.hip)
-// executes them into their arena slots
-constexpr uint32_t kZsFast = 3;
+// DeviceJob::inf_state: where the first pass left a gzip / zstd member
+enum InfState : uint32_t {
+    kInfDecoded = 0,    // decoded and checked, the bytes wait in scratch (inf_off): k_inflate_copy moves them
+    kInfRejected = 1,   // the stream is rejected
+    kInfAgain = 2,      // the output outgrew its scratch slot (or the pool ran out): k_members decodes it
+                        // again, into the arena
+    kZsFast = 3,        // zstd, parsed into records (zstd_fast_item; inf_off -> a ZsFastDesc): k_zexec executes them
+    kZsPending = 4,     // zstd, turned down by k_zplan or k_zparse: k_zfallback runs the wave decoder on it
+    kZsPlanned = 5,     // zstd, sized and planned by k_zplan for k_zparse
+    kZsExact = 6,       // zstd, the decode reached into the overwritten part of the previous ring segment
+                        // (zs::RingDirtyHook): k_zexact decodes it over the exact DCtx-buffer environment
+    kZsExactAgain = 7,  // ... and again into its arena slot (k_zexact's pass 1) when it outgrew the scratch slot
+};
+
+// a kZsFast member's records (rp_inflate.hip zstd_fast_item), at inf_off in
+// the scratch pool; k_zexec (rp_codec.hip) executes them into the arena slot
 constexpr uint32_t kZsFastHdr = 128;  // descriptor bytes before the literal buffer
 struct ZsFastDesc {
     uint64_t nlit, nrec, lit_off, rec_off;  // literal bytes, records; offsets from the descriptor
@@ -174,12 +199,6 @@ struct ZsLitItem {
     uint32_t lsz, seg, ns, hlog, x2;
     uint32_t status;   // 0 not decoded, 1 decoded and every stream ended exactly, 2 decoded, a stream did not
 };
-constexpr uint32_t kZsPlanned = 5;  // inf_state: k_zplan sized and planned the member for k_zparse
-// inf_state: a zstd member whose decode reached into the overwritten part of
-// the previous ring segment (zs::RingDirtyHook): k_zexact decodes it over the
-// exact DCtx-buffer environment (first pass), and again into its arena slot
-// when it outgrew the scratch slot (kZsExactAgain)
-constexpr uint32_t kZsExact = 6, kZsExactAgain = 7;
 
 // one chunk of a large gzip member decoded on its own wave (rp_inflate.hip,
 // k_gzsplan / k_gzsfind / k_gzsdecode / k_gzsresolve)
@@ -201,6 +220,89 @@ constexpr uint32_t kGzsMaxK = 256;     // chunks per member at most
 
 // job counters (DeviceJob::counters), zeroed per submit
 constexpr size_t kCounterBytes = 256;
+// The words of DeviceJob::counters, in slot order: ...Count a list's length
+// (its writer appends), ...Cursor a claim cursor (fetch-add by the kernel
+// that works the list off), ...64 the low word of a 64-bit pair (the next
+// word is its high half: 25, 37, 43).  A new slot takes a free number, in
+// its place below, and leaves the free list.
+// Free: 51..63.
+enum JobCounter : uint32_t {
+    kCtrRewalks = 0,               // k_resolve: chunks walked again; k_finalize_totals -> totals.n_rewalks
+    kCtrOverflowBits = 1,          // the record walks (k_validate, k_validate_decoded, k_walk): bit 1 = index
+                                   // capacity; k_finalize_totals -> totals.overflow
+    kCtrDecodeCount = 2,           // decode_list: k_emit; k_decode, k_crc_compose, k_decode_finish, k_content_xxh,
+                                   // k_content_apply, k_dchain, k_validate_decoded
+    kCtrSplitCount = 3,            // split_list: k_validate; k_crc_split, k_crc_combine, k_finalize_totals (DIAG)
+    kCtrBlockCount = 4,            // blocks reserved (may pass block_capacity): k_decode's planners; k_lz_walk,
+                                   // k_lz_exec
+    kCtrSeqCursor = 5,             // k_decode_blocks over seq_list
+    kCtrSeqCount = 6,              // seq_list: k_decode; k_decode_blocks
+    kCtrLinkCount = 7,             // link_list: plan_lz4f; k_lz_exec
+    kCtrExecCursor = 8,            // k_lz_exec over its units (linked frames, long pieces, chunks of 64 blocks)
+    kCtrSlabCursor = 9,            // the record slab pool's bump cursor: k_lz_walk (walk_long, the lane walk)
+    kCtrLaneCursor = 10,           // k_lz_walk's lane loop over lane_list
+    kCtrLongCount = 11,            // long_list: k_decode's planners; k_lz_exec
+    kCtrComposeCursor = 12,        // k_crc_compose over the decode list
+    kCtrDecodedCursor = 13,        // k_validate_decoded over the decode, member and host lists
+    kCtrFinishCursor = 14,         // k_decode_finish's phase 1 (frames without a content checksum) over the decode list
+    kCtrSplitCursor = 15,          // k_crc_split over split_list
+    kCtrInfCount = 16,             // inf_list: k_emit; every member kernel of rp_inflate.hip, k_zexec, k_dchain,
+                                   // k_validate_decoded
+    kCtrMembersFirstCursor = 17,   // k_members_first passes 0 / 1, phase 0 (members >= 128 KiB) over inf_list
+    kCtrMembersCursor = 18,        // k_members over inf_list
+    kCtrHostCount = 19,            // host_list: k_emit; host_codec_step (copied to the host), k_host_desc, k_dchain,
+                                   // k_validate_decoded
+    kCtrMembersFirstCursor2 = 20,  // k_members_first passes 0 / 1, phase 1 (the rest)
+    kCtrZexecCursor = 21,          // k_zexec over inf_list
+    kCtrZparseCursor = 22,         // k_zparse phase 0 (members >= 128 KiB) over inf_list
+    kCtrZparseCursor2 = 23,        // k_zparse phase 1 (the rest)
+    // Words 24..25 have two users.  kCtrInfScratchUsed64 is the bump allocator
+    // of the gzip / zstd first-pass pool (DeviceJob::inf_scratch_used points
+    // at it): every first-pass kernel of rp_inflate.hip adds to it.
+    // kCtrRawBytes64 is the bytes k_raw_copy copied, k_crc_compose's gate
+    // (it returns unless 2 x raw bytes >= data_len).  The allocator is not
+    // disturbed: its kernels all run in the members stage, which wholly
+    // precedes the decode stage on the job's stream, and nothing allocates
+    // after that.  The gate is loosened: in a job with gzip / zstd members
+    // and LZ4F raw blocks (benchmark stanza C6) the raw bytes start from what
+    // the members reserved from the pool, so k_crc_compose may run where raw
+    // blocks are a minority.  Results are the same (k_validate streams what
+    // is not composed); the speed is unmeasured.
+    kCtrInfScratchUsed64 = 24,
+    kCtrRawBytes64 = 24,
+    kCtrZfallbackCursor = 26,      // k_zfallback over inf_list
+    kCtrZexactCount = 27,          // members marked kZsExact: zstd_first_item; k_zexact (0: nothing to do)
+    kCtrZsItemCount = 28,          // zs_items (may pass zs_items_cap): k_zplan; k_zlits
+    kCtrZlitsCursor = 29,          // k_zlits over zs_items
+    kCtrZplanCursor = 30,          // k_zplan over inf_list
+    kCtrZexactWork = 31,           // k_zexact's buffers, pool offset / 16 + 1 (0: none): its pass 0; its pass 1
+    kCtrGzsItemCount = 32,         // gzs_items (may pass gzs_items_cap): k_gzsplan; k_gzsfind, k_gzsdecode
+    kCtrGzsFindCursor = 33,        // k_gzsfind over gzs_items
+    kCtrGzsDecodeCursor = 34,      // k_gzsdecode over gzs_items
+    kCtrGzsResolveCursor = 35,     // k_gzsresolve over inf_list
+    kCtrGzsPoolUsed64 = 36,        // gzs_pool symbols used (bump allocator): k_gzsdecode
+    kCtrWlongCount = 38,           // wlong_list: k_decode's planners; k_lz_walk
+    kCtrWlongCursor = 39,          // k_lz_walk's wave walk over wlong_list
+    kCtrRawCount = 40,             // raw_list: plan_lz4f; k_raw_copy, k_crc_compose (0: nothing to compose)
+    kCtrLaneCount = 41,            // lane_list (may pass block_capacity): k_decode's planners; k_lz_walk
+    kCtrFrecsUsed64 = 42,          // frecs records reserved (bump allocator): plan_lz4f (note_fast)
+    // one cursor, two kernels: k_decode_finish's phase 0 (the checksummed
+    // frames first) and k_content_xxh, both over the decode list.  `defer`
+    // makes k_decode_finish skip its phase 0 exactly when k_content_xxh runs.
+    kCtrXxhCursor = 44,
+    kCtrLzfCount = 45,             // lzf_list: plan_lz4f (note_fast); k_lzf_walk
+    kCtrLzfCursor = 46,            // k_lzf_walk over lzf_list
+    kCtrLzfTailCount = 47,         // lzf_tail: k_lzf_walk; k_lzf_tail
+    kCtrMembersFirstP2Cursor = 48,   // k_members_first pass 2, phase 0
+    kCtrMembersFirstP2Cursor2 = 49,  // k_members_first pass 2, phase 1
+    kCtrComposeStored = 50,        // RPGPU_DIAG builds only: crcs k_crc_compose stored; k_finalize_totals ->
+                                   // totals.reserved[0]
+    kCtrCount = 51
+};
+static_assert(kCtrInfScratchUsed64 % 2 == 0 && kCtrRawBytes64 % 2 == 0 && kCtrGzsPoolUsed64 % 2 == 0 &&
+                  kCtrFrecsUsed64 % 2 == 0,
+              "a 64-bit pair starts at an even word");
+static_assert(kCtrCount * sizeof(uint32_t) <= kCounterBytes, "the counter block holds every slot");
 
 // Stored payloads with at most kLaneWalkMax records are walked one lane per
 // batch by k_walk; k_validate walks the rest (and decoded payloads) with the
@@ -258,33 +360,16 @@ struct DeviceJob {
     rpgpu_job_totals* totals;
     uint64_t* bitmap;
     const Tables* tables;
-    uint32_t* counters;           // [0] rewalks, [1] overflow bits, [2] decode items, [3] split batches,
-                                  // [4] block items reserved, [5] sequential-frame claim cursor,
-                                  // [6] sequential frames, [7] linked frames, [8] k_lz_exec claim cursor,
-                                  // [9] slab pool cursor, [10] k_lz_walk lane_list cursor, [11] long pieces,
-                                  // [12] (unused), [13] k_validate_decoded claim cursor,
-                                  // [14] k_decode_finish claim cursor, [15] k_crc_split claim cursor,
-                                  // [16] gzip / zstd members (inf_list), [17] k_members_first / [18] k_members claim cursors,
-                                  // [19] host-decoded members (host_list), [20] k_members_first's second claim cursor,
-                                  // [21] k_zexec claim cursor, [22] / [23] k_zparse claim cursors, [26] k_zfallback claim cursor,
-                                  // [28] planned literal blocks (zs_items), [29] k_zlits / [30] k_zplan claim cursors,
-                                  // [32] gzip split items (gzs_items), [33] / [34] / [35] k_gzsfind / k_gzsdecode /
-                                  // k_gzsresolve claim cursors, [36..37] gzs_pool symbols used (u64),
-                                  // [38] / [39] wlong_list count / cursor, [40] raw_list count, [41] lane_list count,
-                                  // [42..43] frecs used (u64), [45] lzf_list count, [46] k_lzf_walk claim cursor,
-                                  // [47] lzf_tail count; [12] k_crc_compose claim cursor, [24..25] bytes
-                                  // k_raw_copy copied (u64), [44] k_decode_finish's checksummed-frame claim cursor,
-                                  // [27] zstd members for k_zexact, [31] k_zexact's buffers (pool offset / 16 + 1),
-                                  // [48] / [49] k_members_first's claim cursors of its pass 2,
-                                  // [50] crcs k_crc_compose stored (RPGPU_DIAG builds only)
-    uint32_t* decode_list;        // batch_capacity: ordinals of batches to uncompress
-    uint32_t* seq_list;           // batch_capacity: decode items decoded whole by one lane
+    uint32_t* counters;           // kCounterBytes: the words JobCounter names
+    uint32_t* decode_list;        // batch_capacity: ordinals of batches to uncompress (kCtrDecodeCount)
+    uint32_t* seq_list;           // batch_capacity: decode items decoded whole by one lane (kCtrSeqCount, kCtrSeqCursor)
     uint32_t* link_list;          // batch_capacity: decode items whose linked LZ4F blocks one wave decodes in order
-    uint32_t* long_list;          // block_capacity: pieces k_lz_exec runs alone ([11] count)
+                                  // (kCtrLinkCount)
+    uint32_t* long_list;          // block_capacity: pieces k_lz_exec runs alone (kCtrLongCount)
     uint32_t* wlong_list;         // block_capacity: the long pieces k_lz_walk may walk one wave each (not
-                                  // k_lzf_walk's; [38] count, [39] cursor)
+                                  // k_lzf_walk's; kCtrWlongCount, kCtrWlongCursor)
     uint32_t* split_list;         // split_capacity: stored payloads >= kSplitMin whose CRC runs in kSplitParts
-                                  // chunks on separate waves ([3] count)
+                                  // chunks on separate waves (kCtrSplitCount)
     uint32_t* split_part;         // split_capacity * kSplitParts: the chunks' linear CRCs
     uint32_t split_capacity;
     uint64_t split_min;           // payloads this large are split: max(kSplitMin, 2 x the job's bytes per k_validate wave)
@@ -299,19 +384,21 @@ struct DeviceJob {
     uint32_t pool_slabs;
     uint2* frecs;                 // LZ4 sequence records of k_lzf_walk (executed by k_lz_exec), 8 B each
     uint64_t frec_cap;            // records frecs holds
-    uint32_t* lzf_list;           // block_capacity: blocks k_lzf_walk takes (planner-listed, [45] count)
-    uint32_t* lane_list;          // block_capacity: the blocks k_lz_walk's lane loop considers ([41] count, [10] cursor)
-    uint32_t* raw_list;           // block_capacity: independent raw blocks k_raw_copy copies ([40] count)
-    uint32_t* lzf_tail;           // block_capacity: blocks whose tails k_lzf_tail runs ([47] count)
-    BlockItem* blocks;            // block work list ([4] items reserved, [5] claim cursor)
+    uint32_t* lzf_list;           // block_capacity: blocks k_lzf_walk takes (planner-listed; kCtrLzfCount, kCtrLzfCursor)
+    uint32_t* lane_list;          // block_capacity: the blocks k_lz_walk's lane loop considers (kCtrLaneCount,
+                                  // kCtrLaneCursor)
+    uint32_t* raw_list;           // block_capacity: independent raw blocks k_raw_copy copies (kCtrRawCount)
+    uint32_t* lzf_tail;           // block_capacity: blocks whose tails k_lzf_tail runs (kCtrLzfTailCount)
+    BlockItem* blocks;            // block work list (kCtrBlockCount items reserved; k_lz_exec takes them in
+                                  // chunks of 64 off kCtrExecCursor)
     uint32_t block_capacity;
     FramePlan* plans;             // one per decode item
     uint32_t* seg_first_bad;      // n_segments: first chain ordinal failing complete && crc_ok (atomicMin)
     const uint64_t* seeds;        // optional chain seeds (index-seeded discovery), per segment ascending
     const uint64_t* seed_off;     // n_segments + 1
-    uint32_t* inf_list;           // batch_capacity: ordinals of gzip / zstd batches (k_members_first / k_members)
-    uint32_t* inf_state;          // batch_capacity: 0 decoded into scratch, 1 rejected, 2 decode again (k_inflate),
-                                  // kZsFast parsed into records (k_zexec), 4 left by k_zparse to k_zfallback
+    uint32_t* inf_list;           // batch_capacity: ordinals of gzip / zstd batches (k_members_first / k_members;
+                                  // kCtrInfCount)
+    uint32_t* inf_state;          // batch_capacity: each member's InfState
     uint64_t* inf_off;            // batch_capacity: scratch offset of each member's first-pass output
     uint64_t* inf_total;          // batch_capacity: decoded bytes of each member
     uint8_t* inf_scratch;         // first-pass output pool (context scratch)
@@ -461,7 +548,13 @@ struct CompactArgs {
     uint32_t* bplen;          // nb: output payload bytes per source batch
     uint64_t* spos;           // nb: rpgpu_stamp positions of the output batches
     uint32_t* splen;          // nb: their payload lengths
-    uint32_t* counters;       // [0] key compare mismatches, [1] batches to stamp, [2] k_stamp's claim cursor
+    uint32_t* counters;       // the words CompactCounter names
+};
+enum CompactCounter : uint32_t {
+    kCcKeyMismatches = 0,  // key compare mismatches: k_cinsert; k_cplan -> the totals
+    kCcStampCount = 1,     // batches to stamp: k_cplan; k_stamp (its d_n)
+    kCcStampCursor = 2,    // k_stamp's claim cursor
+    kCcCount = 3
 };
 hipError_t launch_compact_insert(const CompactArgs& a, uint32_t cus, hipStream_t s);  // eligibility + key insert
 hipError_t launch_compact_keep(const CompactArgs& a, uint32_t cus, hipStream_t s);
@@ -484,8 +577,13 @@ struct AppendArgs {
     uint64_t* bstep;          // nb + 1: offset step (last_offset_delta + 1) per appended batch -> exclusive scan
     uint64_t* spos;           // nb: rpgpu_stamp positions of the append-time batches
     uint32_t* splen;          // nb: their payload lengths
-    uint32_t* counters;       // [0] append-time batches to stamp, [1] k_stamp's claim cursor
+    uint32_t* counters;       // the words AppendCounter names
     const Tables* tables;
+};
+enum AppendCounter : uint32_t {
+    kAcStampCount = 0,   // append-time batches to stamp: k_append_copy lists them; k_stamp (its d_n)
+    kAcStampCursor = 1,  // k_stamp's claim cursor
+    kAcCount = 2
 };
 hipError_t launch_append_sizes(const AppendArgs& a, hipStream_t s);   // verdicts, then sizes / counts / steps
 hipError_t launch_append_plan(const AppendArgs& a, hipStream_t s);    // after the scans: sets, summaries, totals

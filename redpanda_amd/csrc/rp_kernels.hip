@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void k_resolve(DeviceJob j) {
                 j.chunks[c0 + wf] = nr;
                 j.chunk_count[c0 + wf] = o.count;
                 j.chunk_entry[c0 + wf] = entry;
-                atomicAdd(&j.counters[0], 1u);
+                atomicAdd(&j.counters[kCtrRewalks], 1u);
                 if (o.term >= 0) {
                     s_st.pos = o.tpos; s_st.errc = o.term & 0xFF; s_st.eof = (o.term >> 8) & 1;
                     s_ended = 1;
@@ -624,15 +624,15 @@ __global__ __launch_bounds__(256) void k_emit(DeviceJob j) {
             }
             // decode work list for k_decode (order is irrelevant: every item
             // writes only its own batch and its own reserved arena slot)
-            if (complete && decodable) j.decode_list[atomicAdd(&j.counters[2], 1u)] = (uint32_t)ord;
+            if (complete && decodable) j.decode_list[atomicAdd(&j.counters[kCtrDecodeCount], 1u)] = (uint32_t)ord;
             // gzip and zstd members: sized by k_members_first (dcap /
             // slots above are 0 until then)
             if (complete && (j.flags & RPGPU_JOB_DECODE) &&
                 (codec == RPGPU_CODEC_GZIP || (codec == RPGPU_CODEC_ZSTD && !host_codec)))
-                j.inf_list[atomicAdd(&j.counters[16], 1u)] = (uint32_t)ord;
+                j.inf_list[atomicAdd(&j.counters[kCtrInfCount], 1u)] = (uint32_t)ord;
             // zstd members with RPGPU_JOB_HOST_CODECS: decoded by the host step
             if (complete && codec == RPGPU_CODEC_ZSTD && host_codec)
-                j.host_list[atomicAdd(&j.counters[19], 1u)] = (uint32_t)ord;
+                j.host_list[atomicAdd(&j.counters[kCtrHostCount], 1u)] = (uint32_t)ord;
         }
         if (!complete) break;
         p += RPGPU_HEADER_SIZE + h.need;
@@ -837,17 +837,17 @@ __global__ void k_finalize_totals(DeviceJob j) {
     t.batch_capacity_needed = nb_total;
     t.record_capacity_needed = j.slots[nb];
     t.decoded_capacity_needed = dtot;
-    uint32_t ov = j.counters[1];
+    uint32_t ov = j.counters[kCtrOverflowBits];
     if (nb_total > j.batch_capacity) ov |= 1;
     if (j.slots[nb] > j.record_capacity) ov |= 2;
     if (dtot > j.decoded_capacity) ov |= 4;
     t.overflow = ov;
-    t.n_rewalks = j.counters[0];
+    t.n_rewalks = j.counters[kCtrRewalks];
     t.reserved[0] = t.reserved[1] = 0;
 #ifdef RPGPU_DIAG
     // the diagnostic build shows that the split and compose paths ran: payloads
     // listed for k_crc_split (low half), crcs k_crc_compose stored (high half)
-    t.reserved[0] = (uint64_t)j.counters[3] | ((uint64_t)j.counters[50] << 32);
+    t.reserved[0] = (uint64_t)j.counters[kCtrSplitCount] | ((uint64_t)j.counters[kCtrComposeStored] << 32);
 #endif
     *j.totals = t;
 }
@@ -861,7 +861,7 @@ __global__ void k_finalize_totals(DeviceJob j) {
 // record_count
 __global__ __launch_bounds__(256) void k_host_desc(DeviceJob j, HostItem* items) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= j.counters[19]) return;
+    if (i >= j.counters[kCtrHostCount]) return;
     const uint32_t b = j.host_list[i];
     const rpgpu_batch_result& R = j.batches[b];
     HostItem it;

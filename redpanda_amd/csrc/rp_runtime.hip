@@ -619,7 +619,7 @@ int grow_staging(rpgpu_ctx* c, Buf& b, size_t want, hipStream_t s) {
 int host_codec_step(rpgpu_ctx* c, const DeviceJob& j, hipStream_t s) {
     if (int rc = grow_staging(c, c->hc_small, 64, s)) return rc;
     uint32_t* cnt = (uint32_t*)c->hc_small.p;
-    HIPCHK(c, hipMemcpyAsync(cnt, j.counters + 19, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(cnt, j.counters + kCtrHostCount, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const uint32_t n = *cnt;
     if (n == 0) return RPGPU_OK;
@@ -901,7 +901,7 @@ int bind_job(rpgpu_ctx* c, const rpgpu_job* job, const Layout& L, hipStream_t s,
     // members); failing to get it costs a second pass, never the job.
     j.inf_scratch = nullptr;
     j.inf_scratch_bytes = 0;
-    j.inf_scratch_used = (uint64_t*)(j.counters + 24);  // zeroed with the counters
+    j.inf_scratch_used = (uint64_t*)(j.counters + kCtrInfScratchUsed64);  // zeroed with the counters
     if (dec && stop == kRunAll) {
         const size_t want = diag().inf_pool ? diag().inf_pool
                                             : std::min<size_t>(std::max<size_t>(2 * data_len, 256ull << 20), 2ull << 30);
@@ -1461,7 +1461,7 @@ int rpgpu_compact(rpgpu_ctx* c, const rpgpu_compact_job* job, void* stream) {
     const uint64_t nstamp = std::min<uint64_t>(nb, job->out_batch_capacity);
     if (nstamp)
         HIPCHK(c, launch_stamp(job->d_out, a.spos, a.splen, nullptr, 0, (uint32_t)nstamp, RPGPU_STAMP_CRC, c->d_tables,
-                               a.counters + 2, c->cu_count, s, a.counters + 1));
+                               a.counters + kCcStampCursor, c->cu_count, s, a.counters + kCcStampCount));
     HIPCHK(c, mark(5));
     c->cev_live = timed;
     return scratch.release();
@@ -1567,7 +1567,7 @@ int rpgpu_append_wire(rpgpu_ctx* c, const rpgpu_append_job* job, void* stream) {
     const uint64_t nstamp = std::min<uint64_t>(nb, job->out_batch_capacity);
     if (nstamp && job->d_append_time)
         HIPCHK(c, launch_stamp(job->d_out, a.spos, a.splen, nullptr, 0, (uint32_t)nstamp, RPGPU_STAMP_CRC, c->d_tables,
-                               a.counters + 1, c->cu_count, s, a.counters));
+                               a.counters + kAcStampCursor, c->cu_count, s, a.counters + kAcStampCount));
     HIPCHK(c, mark(4));
     if (nb) HIPCHK(c, launch_append_meta(a, s));
     HIPCHK(c, mark(5));

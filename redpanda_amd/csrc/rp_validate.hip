@@ -837,7 +837,7 @@ DEV uint32_t walk_flags(const DeviceJob& j, const WalkResult& w, bool idx_ok, ui
     }
     if (f & RPGPU_F_PARSE_OK) {
         if (idx_ok) f |= RPGPU_F_INDEX_WRITTEN;
-        else { perr = RPGPU_PARSE_ERR_INDEX_CAPACITY; if (lane_v() == 0) atomicOr(&j.counters[1], 2u); }
+        else { perr = RPGPU_PARSE_ERR_INDEX_CAPACITY; if (lane_v() == 0) atomicOr(&j.counters[kCtrOverflowBits], 2u); }
     }
     return f;
 }
@@ -1174,7 +1174,7 @@ DEV void lane_walk_finish(const WalkCtx& j, uint64_t b, const WalkResult& w, boo
     }
     if (f & RPGPU_F_PARSE_OK) {
         if (idx_ok) f |= RPGPU_F_INDEX_WRITTEN;
-        else { perr = RPGPU_PARSE_ERR_INDEX_CAPACITY; atomicOr(&j.counters[1], 2u); }
+        else { perr = RPGPU_PARSE_ERR_INDEX_CAPACITY; atomicOr(&j.counters[kCtrOverflowBits], 2u); }
     }
     // wire: a failed sync record parse is the first batch do_load_slice
     // rejects (kafka/protocol/batch_reader.cc:129-151)
@@ -1266,7 +1266,7 @@ __global__ __launch_bounds__(1024) void k_validate(DeviceJob j) {
             // adapt() parses records only after both checks passed
             // (kafka/protocol/kafka_batch_adapter.cc:157-181)
             if (split) {
-                if (l == 0) j.split_list[atomicAdd(&j.counters[3], 1u)] = (uint32_t)b;
+                if (l == 0) j.split_list[atomicAdd(&j.counters[kCtrSplitCount], 1u)] = (uint32_t)b;
             } else if (crc == d.crc && (!wire || (f & RPGPU_F_WIRE_V2))) {
                 f |= RPGPU_F_CRC_OK;
             } else if (!wire) {
@@ -1335,12 +1335,12 @@ DEV uint64_t split_cut(uint64_t n, uint32_t k) { return k >= kSplitParts ? n : (
 
 __global__ __launch_bounds__(1024) void k_crc_split(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t count = j.counters[3];
+    const uint32_t count = j.counters[kCtrSplitCount];
     if (count == 0) return;
     init_lds_tables(lds, j.tables);
     const Keys K = make_keys();
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[15], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrSplitCursor], 1u);
         if (i >= count * kSplitParts) break;
         const uint32_t item = i / kSplitParts, part = i % kSplitParts;
         const uint64_t b = uni32(j.split_list[item]);
@@ -1361,7 +1361,7 @@ __global__ __launch_bounds__(1024) void k_crc_split(DeviceJob j) {
 // prefix state, an xor over the wave merges them; then the verdict
 __global__ __launch_bounds__(256) void k_crc_combine(DeviceJob j) {
     const uint32_t item = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= j.counters[3]) return;
+    if (item >= j.counters[kCtrSplitCount]) return;
     const uint32_t l = lane_v();
     const uint64_t b = uni32(j.split_list[item]);
     const Desc d = desc_of(load_desc_raw(j, b));
@@ -1399,13 +1399,13 @@ DEV uint32_t wave_sum_u32(uint32_t v) {
 }
 __global__ __launch_bounds__(1024) void k_crc_compose(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t count = j.counters[2];
+    const uint32_t count = j.counters[kCtrDecodeCount];
     // worth it only when raw blocks are most of the job's stored bytes (C2:
     // 12 of 12.9 GB); otherwise k_validate streams every payload as before
     // (C5, a few raw blocks among snappy and compressed LZ4: the kernel's
     // pass over the decode list cost more than it saved)
-    const uint64_t raw_bytes = *(const volatile uint64_t*)(j.counters + 24);
-    if (count == 0 || j.counters[40] == 0 || 2 * raw_bytes < j.data_len) return;
+    const uint64_t raw_bytes = *(const volatile uint64_t*)(j.counters + kCtrRawBytes64);
+    if (count == 0 || j.counters[kCtrRawCount] == 0 || 2 * raw_bytes < j.data_len) return;
     init_lds_tables(lds, j.tables);
     const Keys K = make_keys();
     const uint32_t l = lane_v(), c40 = uni32(j.tables->c40);
@@ -1430,9 +1430,9 @@ __global__ __launch_bounds__(1024) void k_crc_compose(DeviceJob j) {
         return crc_stream(lds, K, st, v, gt, state);
     };
     for (;;) {
-        const uint32_t item = wave_fetch_add(&j.counters[12], 1u);
+        const uint32_t item = wave_fetch_add(&j.counters[kCtrComposeCursor], 1u);
         if (item >= count) break;
-        if (uni32(j.plans[item].mode) != 1u) continue;
+        if (uni32(j.plans[item].mode) != kFrameLz4f) continue;
         const uint32_t first = uni32(j.plans[item].first), nb = uni32(j.plans[item].nb);
         // composed only where raw blocks are most of a large payload: a
         // payload of mostly compressed blocks streams faster through
@@ -1464,7 +1464,7 @@ __global__ __launch_bounds__(1024) void k_crc_compose(DeviceJob j) {
             R->crc_computed = ~state;
             R->reserved0 = (uint16_t)(R->reserved0 | 2u);
 #ifdef RPGPU_DIAG
-            atomicAdd(&j.counters[50], 1u);  // reported by k_finalize_totals (tests/diag_cases.py)
+            atomicAdd(&j.counters[kCtrComposeStored], 1u);  // reported by k_finalize_totals (tests/diag_cases.py)
 #endif
         }
     }
@@ -1485,7 +1485,8 @@ __global__ __launch_bounds__(256) void k_dchain(DeviceJob j) {
     // SIMD's VALU busy back to back (its quarter-rate multiply per stripe), and
     // a chain lane waiting behind it held k_dchain's end with it (0.9 -> 1.9 ms)
     __builtin_amdgcn_s_setprio(kDchainPrio);
-    const uint32_t nlz = j.counters[2], ngz = j.counters[16], count = nlz + ngz + j.counters[19];
+    const uint32_t nlz = j.counters[kCtrDecodeCount], ngz = j.counters[kCtrInfCount],
+                   count = nlz + ngz + j.counters[kCtrHostCount];
     const uint8_t* const aend = j.decoded + j.decoded_capacity;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
         const uint64_t b = i < nlz ? j.decode_list[i] : i < nlz + ngz ? j.inf_list[i - nlz] : j.host_list[i - nlz - ngz];
@@ -1537,17 +1538,18 @@ __global__ __launch_bounds__(256) void k_dchain(DeviceJob j) {
 __global__ __launch_bounds__(1024) void k_validate_decoded(DeviceJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     // the LZ4 / snappy decode list, then the gzip members
-    const uint32_t nlz = j.counters[2], ngz = j.counters[16], count = nlz + ngz + j.counters[19];
+    const uint32_t nlz = j.counters[kCtrDecodeCount], ngz = j.counters[kCtrInfCount],
+                   count = nlz + ngz + j.counters[kCtrHostCount];
     if (count == 0) return;
     const Tables* T = j.tables;
     init_lds_tables(lds, T);
     const uint32_t l = lane_v();
     const Keys K = make_keys();
     const uint32_t c40 = uni32(T->c40);
-    // items claimed one at a time (counters[13]): payloads run 200 B .. 1 MiB,
+    // items claimed one at a time (kCtrDecodedCursor): payloads run 200 B .. 1 MiB,
     // and a static stride left waves holding several of the largest
     for (;;) {
-        const uint32_t i = wave_fetch_add(&j.counters[13], 1u);
+        const uint32_t i = wave_fetch_add(&j.counters[kCtrDecodedCursor], 1u);
         if (i >= count) break;
         const uint64_t b = uni32(i < nlz ? j.decode_list[i] : i < nlz + ngz ? j.inf_list[i - nlz] : j.host_list[i - nlz - ngz]);
         rpgpu_batch_result* R = &j.batches[b];

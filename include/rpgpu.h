@@ -775,6 +775,185 @@ size_t rpgpu_append_sizeof(int which);
  * call's last event. */
 int rpgpu_append_timings(rpgpu_ctx* ctx, float* ms, int n);
 
+/* ------------------------------------------------------------------------ */
+/* Fetch path: the log read of a Kafka fetch, many partitions per call.      */
+/* storage::log_reader over the partition's segments, driven by              */
+/* skipping_consumer (storage/log_reader.cc:26-119, :212-343) under a        */
+/* log_reader_config (storage/types.h:201-270); the accepted batches folded  */
+/* through kafka_batch_serializer (kafka/protocol/batch_consumer.h:27-78)    */
+/* into the partition's wire record set (kafka/server/handlers/fetch.cc:     */
+/* 128-173).  disk_log_impl::timequery is the same read with a 2048-byte     */
+/* budget and a timestamp bound (storage/disk_log_impl.cc:861-917).          */
+/* ------------------------------------------------------------------------ */
+enum rpgpu_fetch_status {
+    RPGPU_FETCH_OK = 0,
+    RPGPU_FETCH_OFFSETS = 1,         /* a visited batch's base_offset lies below the consumer's expected offset:
+                                        the reference throws "incorrect offset encountered reading from disk log" */
+    RPGPU_FETCH_SOURCE_OVERFLOW = 2, /* the source job's totals.overflow != 0: every partition gets this */
+};
+
+/* rpgpu_fetch_request.flags */
+#define RPGPU_FETCH_STRICT_MAX_BYTES (1u << 0) /* log_reader_config::strict_max_bytes */
+#define RPGPU_FETCH_TYPE_FILTER (1u << 1)      /* type_filter has a value (type 0 is a legal value) */
+#define RPGPU_FETCH_FIRST_TIMESTAMP (1u << 2)  /* first_timestamp has a value */
+
+/* Per partition: the log_reader_config of its read.  40 bytes. */
+typedef struct rpgpu_fetch_request {
+    int64_t start_offset;    /* inclusive */
+    int64_t max_offset;      /* inclusive */
+    uint64_t max_bytes;
+    int64_t first_timestamp; /* with RPGPU_FETCH_FIRST_TIMESTAMP */
+    uint32_t flags;          /* RPGPU_FETCH_*; other bits are ignored */
+    int8_t type_filter;      /* with RPGPU_FETCH_TYPE_FILTER */
+    uint8_t pad[3];
+} rpgpu_fetch_request;
+
+/* Per partition.  64 bytes. */
+typedef struct rpgpu_fetch_part {
+    uint32_t status;         /* rpgpu_fetch_status; not OK: nothing written, n_batches = bytes_out = 0 */
+    uint32_t over_budget;    /* log_reader_config::over_budget when the read ended */
+    uint64_t n_batches;      /* batches returned */
+    uint32_t first_out;      /* their first slot in d_out_batches (slots are counted in 32 bits:
+                                out_batch_capacity < 2^31) */
+    uint32_t record_count;   /* kafka_batch_serializer::result::record_count: the returned batches' record_count
+                                summed with uint32 wraparound, as the serializer does.  It shares first_out's
+                                eight bytes so that the struct stays 64 bytes */
+    uint64_t bytes_out;
+    int64_t base_offset;     /* kafka_batch_serializer::result; INT64_MIN (model::offset{}) when nothing was returned */
+    int64_t last_offset;     /* likewise.  With RPGPU_FETCH_OFFSETS the two hold what the reference's exception
+                                names: base_offset the expected batch offset, last_offset the actual one */
+    int64_t next_offset;     /* _config.start_offset when the read ended: the next fetch's start */
+    int64_t first_timestamp; /* the first returned batch's (timequery_result.time); -1 when none */
+} rpgpu_fetch_part;
+
+/* One entry per returned batch, in output order.  16 bytes. */
+typedef struct rpgpu_fetch_batch {
+    uint64_t out_pos;   /* its wire header's position in d_out */
+    uint32_t src_batch; /* job-wide ordinal of the source batch */
+    uint32_t partition;
+} rpgpu_fetch_batch;
+
+/* Whole call.  64 bytes. */
+typedef struct rpgpu_fetch_totals {
+    uint64_t parts_ok;
+    uint64_t batches_out;
+    uint64_t bytes_out;
+    uint64_t out_capacity_needed;       /* bytes_out + 16 */
+    uint64_t out_batch_capacity_needed; /* batches_out */
+    uint32_t overflow;                  /* bit 0: out_capacity, bit 1: out_batch_capacity too small; nothing is
+                                           then written to d_out / d_out_batches */
+    uint32_t reserved0;
+    uint64_t reserved[2];
+} rpgpu_fetch_totals;
+
+/* All pointers are DEVICE pointers, caller-owned.  The first block is the
+ * input and the outputs of a completed RPGPU_LAYOUT_DISK rpgpu_submit with at
+ * least RPGPU_JOB_CRC (same stream, or synchronised). */
+typedef struct rpgpu_fetch_job {
+    const uint8_t* d_data;
+    const uint64_t* d_seg_offsets;       /* n_segments + 1 */
+    uint32_t n_segments;
+    uint32_t n_partitions;
+    const rpgpu_batch_result* d_batches;
+    uint64_t batch_capacity;             /* a bound of the source job's totals.n_batches (its batch_capacity, or
+                                            the total itself): sizes grids and scratch */
+    const rpgpu_segment_summary* d_summaries;
+    const rpgpu_job_totals* d_totals;
+    /* partition p is the job's segments [d_part_segments[p],
+     * d_part_segments[p + 1]), in log order: n_partitions + 1 ascending
+     * entries; equal neighbours give a partition without segments.  Entries
+     * are clamped to n_segments and to their predecessor on the device. */
+    const uint32_t* d_part_segments;
+    const rpgpu_fetch_request* d_requests; /* n_partitions */
+    /* optional entry index: all three NULL, or the outputs of
+     * rpgpu_segment_index over this job (batch_capacity entries each) */
+    const rpgpu_index_state* d_index_states;
+    const uint32_t* d_rel_offset;
+    const uint64_t* d_position;
+    /* outputs */
+    uint8_t* d_out;                      /* the partitions' record sets back to back; 16-byte aligned */
+    uint64_t out_capacity;               /* bytes, including 16 spare bytes past the last batch: the partitions'
+                                            max_bytes summed, plus each partition's largest batch, plus 16 always
+                                            suffices; so does the source bytes + 16 */
+    uint64_t* d_out_part_offsets;        /* n_partitions + 1: partition p's bytes are [p, p + 1) */
+    rpgpu_fetch_batch* d_out_batches;
+    uint64_t out_batch_capacity;
+    rpgpu_fetch_part* d_parts;           /* n_partitions */
+    rpgpu_fetch_totals* d_ftotals;       /* one */
+} rpgpu_fetch_job;
+
+/* The read, exactly.  Arithmetic on offsets wraps (two's complement int64);
+ * last_offset = base_offset + last_offset_delta.
+ *
+ * A segment's chain for this call is its RPGPU_F_COMPLETE batches, in chain
+ * order (an incomplete batch can only be the last, and the reference never
+ * delivers it).  A segment without one is empty and is skipped.  A segment's
+ * dirty_offset is the last_offset of its last chain batch.  CRC flags play no
+ * part: skipping_consumer does not check the batch crc, a batch without
+ * RPGPU_F_CRC_OK is returned verbatim.  The batch cache is cold, there is no
+ * timeout and no abort source.
+ *
+ * Per partition: start = start_offset, consumed = 0, over_budget = false.
+ * For each non-empty segment in order:
+ *   1. start > dirty_offset: next segment (find_next_valid_iterator).
+ *   2. Otherwise a fresh consumer starts with expected = INT64_MIN,
+ *   3. at the segment's first chain batch, or
+ *   4. with the index arrays at the chain batch whose file_pos is
+ *      segment_index::find_nearest(start)'s position (storage/segment.cc:
+ *      451-459, storage/segment_index.cc:95-120; `start` as it is when the
+ *      segment is entered; needle = (uint32)(start - index_state.base_offset),
+ *      std::lower_bound over the segment's relative offsets, the last entry
+ *      when it runs off the end, then downwards to the first entry <= needle;
+ *      no entry, an empty index or start < base_offset: the first chain
+ *      batch).  If no chain batch has that position, the first one with
+ *      file_pos >= it.
+ * Then for each batch b from there, the first rule that applies:
+ *   1. b.base_offset < expected: status RPGPU_FETCH_OFFSETS, the read ends
+ *      and nothing of the partition is returned.
+ *   2. b.base_offset > max_offset: the read ends.
+ *   3. (strict || consumed != 0) && consumed + (uint64)(int64)b.size_bytes >
+ *      max_bytes, in wrapping uint64 arithmetic: over_budget = true, the
+ *      read ends.
+ *   4. b.last_offset < start: expected = b.last_offset + 1, next batch.
+ *   5. type filter set and != b.type: start = expected = b.last_offset + 1,
+ *      next batch.
+ *   6. first timestamp set and > b.first_timestamp: as 5.
+ *   7. The batch is returned; expected = start = b.last_offset + 1, consumed
+ *      += size_bytes; b.last_offset >= max_offset or consumed > max_bytes:
+ *      the read ends.  With consumed == max_bytes it goes on, and rule 3 ends
+ *      it at the next batch it visits.
+ * Running off a segment's chain moves to the next segment, whatever its
+ * terminal_errc is: a torn or fallocated tail is invisible to a reader, whose
+ * `start` is then past the segment's dirty_offset.  Rule 1 counts only at a
+ * batch the reader visits: not beyond the stop point, and not across
+ * segments (every segment gets a fresh consumer).
+ *
+ * The output: partition p's returned batches in order, each as
+ * kafka::writer_serialize_batch writes it (kafka/protocol/response_writer.h:
+ * 241-276, rpgpu_serialize_wire's transform; base_offset stays the log's),
+ * back to back in d_out[d_out_part_offsets[p], d_out_part_offsets[p + 1]),
+ * the partitions back to back in partition order.  A partition whose status
+ * is not OK returns nothing; its next_offset and over_budget are those of
+ * the moment the read ended (SOURCE_OVERFLOW: start_offset, 0).
+ *
+ * Asynchronous on `stream`; never writes out of bounds: a capacity that is
+ * too small sets d_ftotals->overflow and reports the sizes needed (d_parts
+ * and d_out_part_offsets are written all the same).  NULL or inconsistent
+ * arguments return RPGPU_E_INVALID without touching a device. */
+int rpgpu_fetch(rpgpu_ctx* ctx, const rpgpu_fetch_job* job, void* stream);
+
+/* sizeof of the fetch structs as compiled into the library: 0 =
+ * rpgpu_fetch_request, 1 = rpgpu_fetch_part, 2 = rpgpu_fetch_batch, 3 =
+ * rpgpu_fetch_totals, 4 = rpgpu_fetch_job (0 for any other value). */
+size_t rpgpu_fetch_sizeof(int which);
+
+/* Device time of the last timed rpgpu_fetch (rpgpu_set_timing), in
+ * milliseconds: 0 = whole call, 1 = select, 2 = scans + plan, 3 = copy,
+ * 4 = output metadata (d_out_batches is written by the copy's first piece of
+ * each batch, so this is the empty interval behind it).  Synchronises on the
+ * call's last event. */
+int rpgpu_fetch_timings(rpgpu_ctx* ctx, float* ms, int n);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -14,6 +14,9 @@
  *   storage::continuous_batch_parser      storage/parser.h:94-136 (parser.cc:96-254)
  *   storage::log_replayer                 storage/log_replayer.h/.cc:27-114
  *   compression::compressor::uncompress   compression/compression.h:21-24
+ *   storage::log_reader_config            storage/types.h:201-270
+ *   kafka::read_from_partitions           kafka/server/handlers/fetch.cc:128-173 (storage/log_reader.cc)
+ *   storage::timequery                    storage/disk_log_impl.cc:861-917
  *   kafka::batch_reader,
  *   kafka::kafka_batch_adapter            kafka/protocol/batch_reader.h, batch_reader.cc:50-156,
  *                                         kafka/protocol/kafka_batch_adapter.h:60-76 (.cc:126-188)
@@ -34,6 +37,8 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <functional>
+#include <limits>
 #include <memory>
 #include <algorithm>
 #include <optional>
@@ -1278,5 +1283,240 @@ inline std::vector<partition_append> produce_append(const std::vector<rpgpu::iob
 }
 
 }  // namespace kafka
+
+// ---------------------------------------------------------------------------
+// The fetch path: storage::log_reader under a log_reader_config, folded
+// through kafka_batch_serializer, many partitions per call (rpgpu_fetch)
+// ---------------------------------------------------------------------------
+namespace storage {
+
+// ss::io_priority_class and ss::abort_source have no meaning off Seastar:
+// the fields are kept so that a caller's constructor calls compile
+struct io_priority_class {};
+struct abort_source {};
+using opt_abort_source_t = std::optional<std::reference_wrapper<abort_source>>;
+
+// storage/types.h:201-270.  Start and max offset are inclusive.
+struct log_reader_config {
+    int64_t start_offset;
+    int64_t max_offset;
+    size_t min_bytes;
+    size_t max_bytes;
+    io_priority_class prio;
+    std::optional<int8_t> type_filter;  // model::record_batch_type
+    std::optional<int64_t> first_timestamp;
+    opt_abort_source_t abort_source;  // not consulted: a device read has no abort point
+    size_t bytes_consumed{0};
+    bool over_budget{false};
+    bool strict_max_bytes{false};
+    bool skip_batch_cache{false};  // there is no batch cache here
+
+    log_reader_config(int64_t start_offset, int64_t max_offset, size_t min_bytes, size_t max_bytes, io_priority_class prio,
+                      std::optional<int8_t> type_filter, std::optional<int64_t> time, opt_abort_source_t as)
+      : start_offset(start_offset), max_offset(max_offset), min_bytes(min_bytes), max_bytes(max_bytes), prio(prio),
+        type_filter(type_filter), first_timestamp(time), abort_source(as) {}
+    // read offsets [start, end]
+    log_reader_config(int64_t start_offset, int64_t max_offset, io_priority_class prio,
+                      opt_abort_source_t as = std::nullopt)
+      : log_reader_config(start_offset, max_offset, 0, std::numeric_limits<size_t>::max(), prio, std::nullopt,
+                          std::nullopt, as) {}
+};
+
+}  // namespace storage
+
+namespace kafka {
+
+// kafka_batch_serializer::result (kafka/protocol/batch_consumer.h:29-34) of
+// one partition's read, and where the reader stood when it ended
+struct fetch_result {
+    rpgpu::iobuf data;  // the partition's Kafka v2 record set
+    uint32_t record_count{0};
+    int64_t base_offset{INT64_MIN};  // model::offset{} when nothing was returned
+    int64_t last_offset{INT64_MIN};
+    int64_t next_offset{0};          // log_reader_config::start_offset when the read ended
+    bool over_budget{false};
+    int64_t first_timestamp{-1};     // the first returned batch's; -1 when none
+};
+
+// One fetch over many partitions, through the device in one pass:
+// partitions_segments[p] holds partition p's log segments in log order,
+// configs[p] its log_reader_config.  rpgpu_submit (disk layout, CRC)
+// validates every segment, rpgpu_segment_index rebuilds the segment indexes
+// when use_index is set (each segment's base offset is its first batch's; the
+// reader then enters a segment at segment_index::find_nearest(start_offset)),
+// and rpgpu_fetch reads every partition.  Throws std::runtime_error with
+// skipping_consumer's message where the reference throws
+// (storage/log_reader.cc:30-36).
+inline std::vector<fetch_result> read_from_partitions(const std::vector<std::vector<rpgpu::iobuf>>& partitions_segments,
+                                                      const std::vector<storage::log_reader_config>& configs,
+                                                      bool use_index = false,
+                                                      rpgpu::engine& e = rpgpu::engine::local()) {
+    const size_t np = partitions_segments.size();
+    if (configs.size() != np) throw std::invalid_argument("read_from_partitions: one log_reader_config per partition");
+    std::vector<fetch_result> res(np);
+    if (np == 0) return res;
+    rpgpu_ctx* c = e.ctx();
+    std::vector<uint32_t> part_segs(np + 1, 0);
+    std::vector<uint64_t> offs(1, 0);
+    for (size_t p = 0; p < np; p++) {
+        for (const rpgpu::iobuf& seg : partitions_segments[p]) offs.push_back(offs.back() + seg.size_bytes());
+        part_segs[p + 1] = (uint32_t)(offs.size() - 1);
+    }
+    const size_t nseg = offs.size() - 1, len = (size_t)offs[nseg];
+    std::vector<uint8_t> host(len);
+    {
+        size_t s = 0;
+        for (const auto& part : partitions_segments)
+            for (const rpgpu::iobuf& seg : part) {
+                if (!seg.empty()) std::memcpy(host.data() + offs[s], seg.data(), seg.size_bytes());
+                s++;
+            }
+    }
+    std::vector<rpgpu_fetch_request> reqs(np);
+    for (size_t p = 0; p < np; p++) {
+        const storage::log_reader_config& g = configs[p];
+        rpgpu_fetch_request& q = reqs[p];
+        q = rpgpu_fetch_request{};
+        q.start_offset = g.start_offset;
+        q.max_offset = g.max_offset;
+        q.max_bytes = g.max_bytes;
+        q.first_timestamp = g.first_timestamp.value_or(0);
+        q.type_filter = g.type_filter.value_or(0);
+        q.flags = (g.strict_max_bytes ? RPGPU_FETCH_STRICT_MAX_BYTES : 0u) | (g.type_filter ? RPGPU_FETCH_TYPE_FILTER : 0u) |
+                  (g.first_timestamp ? RPGPU_FETCH_FIRST_TIMESTAMP : 0u);
+    }
+    rpgpu::dev_buffer d_data(e, len + 16), d_offs(e, (nseg + 1) * 8), d_ps(e, (np + 1) * 4),
+        d_rq(e, np * sizeof(rpgpu_fetch_request));
+    e.check(rpgpu_memset(c, (uint8_t*)d_data.get() + len, 0, 16, nullptr), "rpgpu_memset");
+    if (len) e.check(rpgpu_memcpy_h2d(c, d_data.get(), host.data(), len, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_offs.get(), offs.data(), (nseg + 1) * 8, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_ps.get(), part_segs.data(), (np + 1) * 4, nullptr), "rpgpu_memcpy_h2d");
+    e.check(rpgpu_memcpy_h2d(c, d_rq.get(), reqs.data(), np * sizeof(rpgpu_fetch_request), nullptr), "rpgpu_memcpy_h2d");
+    rpgpu_job j{};
+    j.d_data = (const uint8_t*)d_data.get();
+    j.d_seg_offsets = (const uint64_t*)d_offs.get();
+    j.h_seg_offsets = offs.data();
+    j.n_segments = (uint32_t)nseg;
+    j.layout = RPGPU_LAYOUT_DISK;
+    j.flags = RPGPU_JOB_CRC;
+    rpgpu_capacity cap{};
+    e.check(rpgpu_query_capacity(c, &j, nullptr, &cap), "rpgpu_query_capacity");
+    const uint64_t nb = cap.n_batches + 1;
+    rpgpu::dev_buffer d_b(e, nb * sizeof(rpgpu_batch_result)), d_sum(e, (nseg + 1) * sizeof(rpgpu_segment_summary)),
+        d_tot(e, sizeof(rpgpu_job_totals));
+    j.d_batches = (rpgpu_batch_result*)d_b.get();
+    j.batch_capacity = nb;
+    j.d_summaries = (rpgpu_segment_summary*)d_sum.get();
+    j.d_totals = (rpgpu_job_totals*)d_tot.get();
+    e.check(rpgpu_submit(c, &j, nullptr), "rpgpu_submit");
+    rpgpu::dev_buffer d_ist(e, (nseg + 1) * sizeof(rpgpu_index_state)), d_ro(e, nb * 4), d_rt(e, nb * 4), d_pos(e, nb * 8);
+    if (use_index && nseg) {
+        // a segment's base offset is its first batch's (the name of its file)
+        std::vector<rpgpu_segment_summary> sums(nseg);
+        e.check(rpgpu_memcpy_d2h(c, sums.data(), d_sum.get(), nseg * sizeof(rpgpu_segment_summary), nullptr),
+                "rpgpu_memcpy_d2h");
+        e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        std::vector<rpgpu_index_state> ist(nseg, rpgpu_index_state{});
+        for (size_t s = 0; s < nseg; s++) {
+            if (!sums[s].n_batches || sums[s].first_batch >= nb) continue;
+            rpgpu_batch_result first{};
+            e.check(rpgpu_memcpy_d2h(c, &first, (const rpgpu_batch_result*)d_b.get() + sums[s].first_batch, sizeof first,
+                                     nullptr),
+                    "rpgpu_memcpy_d2h");
+            e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+            ist[s].base_offset = first.base_offset;
+        }
+        e.check(rpgpu_memcpy_h2d(c, d_ist.get(), ist.data(), nseg * sizeof(rpgpu_index_state), nullptr), "rpgpu_memcpy_h2d");
+        e.check(rpgpu_segment_index(c, j.d_batches, nb, j.d_summaries, (uint32_t)nseg, RPGPU_INDEX_DEFAULT_STEP,
+                                    (rpgpu_index_state*)d_ist.get(), (uint32_t*)d_ro.get(), (uint32_t*)d_rt.get(),
+                                    (uint64_t*)d_pos.get(), nullptr),
+                "rpgpu_segment_index");
+    }
+    // every returned batch fits the bytes it came in: len + 16 is always enough
+    const uint64_t out_cap = (uint64_t)len + 16;
+    rpgpu::dev_buffer d_out(e, out_cap), d_opo(e, (np + 1) * 8), d_ob(e, nb * sizeof(rpgpu_fetch_batch)),
+        d_parts(e, np * sizeof(rpgpu_fetch_part)), d_ft(e, sizeof(rpgpu_fetch_totals));
+    rpgpu_fetch_job k{};
+    k.d_data = j.d_data;
+    k.d_seg_offsets = j.d_seg_offsets;
+    k.n_segments = (uint32_t)nseg;
+    k.n_partitions = (uint32_t)np;
+    k.d_batches = j.d_batches;
+    k.batch_capacity = nb;
+    k.d_summaries = j.d_summaries;
+    k.d_totals = j.d_totals;
+    k.d_part_segments = (const uint32_t*)d_ps.get();
+    k.d_requests = (const rpgpu_fetch_request*)d_rq.get();
+    if (use_index && nseg) {
+        k.d_index_states = (const rpgpu_index_state*)d_ist.get();
+        k.d_rel_offset = (const uint32_t*)d_ro.get();
+        k.d_position = (const uint64_t*)d_pos.get();
+    }
+    k.d_out = (uint8_t*)d_out.get();
+    k.out_capacity = out_cap;
+    k.d_out_part_offsets = (uint64_t*)d_opo.get();
+    k.d_out_batches = (rpgpu_fetch_batch*)d_ob.get();
+    k.out_batch_capacity = nb;
+    k.d_parts = (rpgpu_fetch_part*)d_parts.get();
+    k.d_ftotals = (rpgpu_fetch_totals*)d_ft.get();
+    e.check(rpgpu_fetch(c, &k, nullptr), "rpgpu_fetch");
+    rpgpu_fetch_totals ft{};
+    std::vector<rpgpu_fetch_part> parts(np);
+    std::vector<uint64_t> out_offs(np + 1);
+    e.check(rpgpu_memcpy_d2h(c, &ft, d_ft.get(), sizeof ft, nullptr), "rpgpu_memcpy_d2h");
+    e.check(rpgpu_memcpy_d2h(c, parts.data(), d_parts.get(), np * sizeof(rpgpu_fetch_part), nullptr), "rpgpu_memcpy_d2h");
+    e.check(rpgpu_memcpy_d2h(c, out_offs.data(), d_opo.get(), (np + 1) * 8, nullptr), "rpgpu_memcpy_d2h");
+    e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+    if (ft.overflow) throw std::runtime_error("read_from_partitions: output capacity");
+    std::vector<uint8_t> bytes((size_t)ft.bytes_out);
+    if (!bytes.empty()) {
+        e.check(rpgpu_memcpy_d2h(c, bytes.data(), d_out.get(), bytes.size(), nullptr), "rpgpu_memcpy_d2h");
+        e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+    }
+    for (size_t p = 0; p < np; p++) {
+        const rpgpu_fetch_part& g = parts[p];
+        if (g.status == RPGPU_FETCH_OFFSETS)
+            throw std::runtime_error("incorrect offset encountered reading from disk log: expected batch offset " +
+                                     std::to_string(g.base_offset) + " (actual " + std::to_string(g.last_offset) + ")");
+        if (g.status != RPGPU_FETCH_OK) throw std::runtime_error("read_from_partitions: the validation job overflowed its outputs");
+        fetch_result& r = res[p];
+        r.data = rpgpu::iobuf(bytes.data() + out_offs[p], (size_t)(out_offs[p + 1] - out_offs[p]));
+        r.record_count = g.record_count;
+        r.base_offset = g.base_offset;
+        r.last_offset = g.last_offset;
+        r.next_offset = g.next_offset;
+        r.over_budget = g.over_budget != 0;
+        r.first_timestamp = g.first_timestamp;
+    }
+    return res;
+}
+
+}  // namespace kafka
+
+namespace storage {
+
+// storage/types.h timequery_result
+struct timequery_result {
+    int64_t offset;
+    int64_t time;
+};
+
+// disk_log_impl::timequery (storage/disk_log_impl.cc:861-917) over one
+// partition's segments: a reader from the log's start with a 2048-byte budget
+// ("we just need one record batch") and first_timestamp = time; the first
+// batch it returns answers the query if its first_timestamp >= time.
+inline std::optional<timequery_result> timequery(const std::vector<rpgpu::iobuf>& segments, int64_t time,
+                                                 int64_t max_offset, rpgpu::engine& e = rpgpu::engine::local()) {
+    if (segments.empty()) return std::nullopt;
+    // make_reader starts at the first segment's base offset: its first batch's
+    int64_t start = 0;
+    if (segments.front().size_bytes() >= RPGPU_HEADER_SIZE) std::memcpy(&start, segments.front().data() + 8, 8);
+    log_reader_config cfg(start, max_offset, 0, 2048, io_priority_class{}, std::nullopt, time, std::nullopt);
+    const std::vector<kafka::fetch_result> r = kafka::read_from_partitions({segments}, {cfg}, false, e);
+    if (!r[0].data.empty() && r[0].first_timestamp >= time) return timequery_result{r[0].base_offset, r[0].first_timestamp};
+    return std::nullopt;
+}
+
+}  // namespace storage
 
 #endif  // RPGPU_REDPANDA_H_

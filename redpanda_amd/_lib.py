@@ -67,6 +67,27 @@ class AppendJobC(C.Structure):
     ]
 
 
+class FetchRequestC(C.Structure):
+    """rpgpu_fetch_request (include/rpgpu.h)."""
+    _fields_ = [("start_offset", C.c_int64), ("max_offset", C.c_int64), ("max_bytes", C.c_uint64),
+                ("first_timestamp", C.c_int64), ("flags", C.c_uint32), ("type_filter", C.c_int8),
+                ("pad", C.c_uint8 * 3)]
+
+
+class FetchJobC(C.Structure):
+    """rpgpu_fetch_job (include/rpgpu.h)."""
+    _fields_ = [
+        ("d_data", C.c_void_p), ("d_seg_offsets", C.c_void_p), ("n_segments", C.c_uint32), ("n_partitions", C.c_uint32),
+        ("d_batches", C.c_void_p), ("batch_capacity", C.c_uint64),
+        ("d_summaries", C.c_void_p), ("d_totals", C.c_void_p),
+        ("d_part_segments", C.c_void_p), ("d_requests", C.c_void_p),
+        ("d_index_states", C.c_void_p), ("d_rel_offset", C.c_void_p), ("d_position", C.c_void_p),
+        ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("d_out_part_offsets", C.c_void_p),
+        ("d_out_batches", C.c_void_p), ("out_batch_capacity", C.c_uint64),
+        ("d_parts", C.c_void_p), ("d_ftotals", C.c_void_p),
+    ]
+
+
 def exported_symbols_from_header(path: str = HEADER):
     """Function names declared in include/rpgpu.h."""
     src = open(path).read()
@@ -136,6 +157,9 @@ def load():
         "rpgpu_append_wire": (i32, [vp, C.POINTER(AppendJobC), vp]),
         "rpgpu_append_sizeof": (sz, [i32]),
         "rpgpu_append_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
+        "rpgpu_fetch": (i32, [vp, C.POINTER(FetchJobC), vp]),
+        "rpgpu_fetch_sizeof": (sz, [i32]),
+        "rpgpu_fetch_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -164,5 +188,6 @@ def crc32c(data, crc: int = 0) -> int:
     return load().rpgpu_crc32c_extend(crc, a.ctypes.data_as(C.c_void_p), a.nbytes)
 
 
-__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "AppendJobC", "RpgpuError", "abi",
+__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "AppendJobC", "FetchJobC",
+           "FetchRequestC", "RpgpuError", "abi",
            "exported_symbols_from_header"]

@@ -144,6 +144,33 @@ APPEND_TOTALS_COMPARE_FIELDS = [n for n in APPEND_TOTALS.names if not n.startswi
 # d_out_summaries: n_records is 0 by contract (the record index stays the source job's)
 APPEND_SUMMARY_COMPARE_FIELDS = [n for n in SEGMENT_SUMMARY.names if n != "reserved"]
 
+# rpgpu_fetch (include/rpgpu.h): the fetch path's log read
+FETCH_OK, FETCH_OFFSETS, FETCH_SOURCE_OVERFLOW = 0, 1, 2
+FETCH_STRICT_MAX_BYTES, FETCH_TYPE_FILTER, FETCH_FIRST_TIMESTAMP = 1 << 0, 1 << 1, 1 << 2
+OFFSET_MIN = -(1 << 63)  # model::offset{}: base_offset / last_offset of a read that returned nothing
+
+FETCH_REQUEST = np.dtype([
+    ("start_offset", "<i8"), ("max_offset", "<i8"), ("max_bytes", "<u8"), ("first_timestamp", "<i8"),
+    ("flags", "<u4"), ("type_filter", "i1"), ("pad", "u1", (3,)),
+])
+assert FETCH_REQUEST.itemsize == 40
+FETCH_PART = np.dtype([
+    ("status", "<u4"), ("over_budget", "<u4"), ("n_batches", "<u8"), ("first_out", "<u4"), ("record_count", "<u4"),
+    ("bytes_out", "<u8"), ("base_offset", "<i8"), ("last_offset", "<i8"), ("next_offset", "<i8"),
+    ("first_timestamp", "<i8"),
+])
+assert FETCH_PART.itemsize == 64
+FETCH_BATCH = np.dtype([("out_pos", "<u8"), ("src_batch", "<u4"), ("partition", "<u4")])
+assert FETCH_BATCH.itemsize == 16
+FETCH_TOTALS = np.dtype([
+    ("parts_ok", "<u8"), ("batches_out", "<u8"), ("bytes_out", "<u8"), ("out_capacity_needed", "<u8"),
+    ("out_batch_capacity_needed", "<u8"), ("overflow", "<u4"), ("reserved0", "<u4"), ("reserved", "<u8", (2,)),
+])
+assert FETCH_TOTALS.itemsize == 64
+FETCH_PART_COMPARE_FIELDS = list(FETCH_PART.names)
+FETCH_BATCH_COMPARE_FIELDS = list(FETCH_BATCH.names)
+FETCH_TOTALS_COMPARE_FIELDS = [n for n in FETCH_TOTALS.names if not n.startswith("reserved")]
+
 # fields of rpgpu_batch_result that are outputs of the engine and compared
 # bit-exactly against the oracle (reserved fields excluded)
 BATCH_COMPARE_FIELDS = [n for n in BATCH_RESULT.names if not n.startswith("reserved")]

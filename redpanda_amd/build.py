@@ -20,7 +20,7 @@ OUT = os.path.join(HERE, "librpgpu.so")
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("RPGPU_ARCH", "gfx950")
 
-HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip",
+HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip", "rp_fetch.hip",
                "rp_runtime.hip"]
 CXX_SOURCES = ["rp_hostcodec.cpp"]
 
@@ -144,6 +144,22 @@ def build_append_test(force: bool = False) -> str:
         _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, APPEND_SRC, "-o", APPEND_BIN, "-L", HERE, "-l:librpgpu.so",
               "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
     return APPEND_BIN
+
+
+FETCH_SRC = os.path.join(ROOT, "tests", "cpp", "fetch_main.cpp")
+FETCH_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "fetch_test")
+
+
+def build_fetch_test(force: bool = False) -> str:
+    """Host driver of kafka::read_from_partitions and storage::timequery
+    (include/rpgpu_redpanda.h), linked like the surfaces driver."""
+    lib = build()
+    hdrs = [os.path.join(INC, "rpgpu.h"), os.path.join(INC, "rpgpu_redpanda.h")]
+    if force or _stale(FETCH_BIN, [FETCH_SRC, lib] + hdrs):
+        os.makedirs(os.path.dirname(FETCH_BIN), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, FETCH_SRC, "-o", FETCH_BIN, "-L", HERE, "-l:librpgpu.so",
+              "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
+    return FETCH_BIN
 
 
 ZSHOST_SRC =os.path.join(ROOT, "tests", "cpp", "zstd_core_host.cpp")

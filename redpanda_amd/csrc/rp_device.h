@@ -286,6 +286,32 @@ DEV void init_lds_hdr(uint32_t* th, const Tables* T) {
     __syncthreads();
 }
 
+// The piece copy of k_append_copy and k_fetch_copy.
+// n bytes from s to d, one wave: 16 bytes per lane and instruction between
+// the destination's 16-byte lines (aligned stores, loads at the source's
+// alignment), the bytes before the first and after the last line one lane
+// each.  Touches [d, d + n) and [s, s + n) only.
+DEV void wave_copy_lines(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, uint32_t n, uint32_t l) {
+    uint32_t head = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
+    if (head > n) head = n;
+    if (l < head) d[l] = s[l];
+    const uint32_t nv = (n - head) >> 4;
+    uint4* __restrict__ dv = (uint4*)(d + head);
+    const uint8_t* __restrict__ sv = s + head;
+    uint32_t i = l;
+    for (; i + 192 < nv; i += 256) {  // four lines per lane in flight
+        const uint4 t0 = ld16u(sv + 16ull * i), t1 = ld16u(sv + 16ull * (i + 64)), t2 = ld16u(sv + 16ull * (i + 128)),
+                    t3 = ld16u(sv + 16ull * (i + 192));
+        dv[i] = t0;
+        dv[i + 64] = t1;
+        dv[i + 128] = t2;
+        dv[i + 192] = t3;
+    }
+    for (; i < nv; i += 64) dv[i] = ld16u(sv + 16ull * i);
+    const uint32_t done = head + (nv << 4), tail = n - done;
+    if (l < tail) d[done + l] = s[done + l];
+}
+
 #define HD __host__ __device__ inline
 
 HD uint32_t rd32h(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }

@@ -590,4 +590,25 @@ hipError_t launch_append_plan(const AppendArgs& a, hipStream_t s);    // after t
 hipError_t launch_append_copy(const AppendArgs& a, uint32_t cus, hipStream_t s);
 hipError_t launch_append_meta(const AppendArgs& a, hipStream_t s);    // after the stamp: d_out_batches
 
+// rp_fetch.hip: fetch-path log read (rpgpu_fetch).  Workspace arrays are
+// context scratch; nb bounds the source job's batch total.  Payloads are
+// copied in pieces of kAppendPiece bytes, one wave each, as the append does.
+// What k_fetch_select leaves per partition for k_fetch_plan.
+struct FetchSel {
+    uint32_t status, over_budget;
+    int64_t base_offset, last_offset, next_offset, first_timestamp;
+};
+struct FetchArgs {
+    rpgpu_fetch_job job;
+    uint64_t nb;              // job.batch_capacity
+    uint64_t* bpos;           // nb + 1: output bytes per source batch (0: not returned) -> exclusive scan
+    uint64_t* bcnt;           // nb + 1: low half 1 per returned batch, high half its copy pieces -> exclusive scan
+    uint64_t* brec;           // nb + 1: record_count (as uint32) per returned batch -> exclusive scan
+    uint32_t* bpart;          // nb: the partition of each returned batch
+    FetchSel* sel;            // n_partitions
+};
+hipError_t launch_fetch_select(const FetchArgs& a, hipStream_t s);  // bpos / bcnt / brec zeroed before
+hipError_t launch_fetch_plan(const FetchArgs& a, hipStream_t s);    // after the scans: parts, offsets, totals
+hipError_t launch_fetch_copy(const FetchArgs& a, uint32_t cus, hipStream_t s);  // payloads, headers, d_out_batches
+
 }  // namespace rp

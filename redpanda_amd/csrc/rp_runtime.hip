@@ -147,6 +147,11 @@ struct rpgpu_ctx {
     Buf aws;
     hipEvent_t aev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool aev_live = false;
+    // rpgpu_fetch workspace (per-batch plan, per-partition read state, scan
+    // temporaries); its stage events (rpgpu_set_timing)
+    Buf fws;
+    hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool fev_live = false;
     // k_lz_exec parse records (kRecsPerLane per lane of each resident wave),
     // allocated on the first decode job
     Buf seqs;
@@ -455,7 +460,7 @@ int rpgpu_destroy(rpgpu_ctx* c) {
         if (sd->join_ev) (void)hipEventDestroy(sd->join_ev);
     }
     if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
-    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->seqs, &c->pool, &c->fpool,
+    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->fws, &c->seqs, &c->pool, &c->fpool,
                    &c->sth, &c->std_, &c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h,
                    &c->hc_small, &c->gz_pool, &c->gzs_pool})
         b->release();
@@ -470,6 +475,8 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     for (hipEvent_t e : c->cev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->aev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->fev)
         if (e) hipEventDestroy(e);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     for (auto& set : c->ev_sets)
@@ -1583,6 +1590,104 @@ int rpgpu_append_timings(rpgpu_ctx* c, float* ms, int n) {
     HIPCHK(c, hipEventElapsedTime(&v[0], c->aev[0], c->aev[5]));
     for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->aev[i - 1], c->aev[i]));
     for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
+    return RPGPU_OK;
+}
+
+// The fetch path's log read over a completed disk-layout job's outputs
+// (kernels in rp_fetch.hip).
+size_t rpgpu_fetch_sizeof(int which) {
+    switch (which) {
+    case 0: return sizeof(rpgpu_fetch_request);
+    case 1: return sizeof(rpgpu_fetch_part);
+    case 2: return sizeof(rpgpu_fetch_batch);
+    case 3: return sizeof(rpgpu_fetch_totals);
+    case 4: return sizeof(rpgpu_fetch_job);
+    default: return 0;
+    }
+}
+
+int rpgpu_fetch(rpgpu_ctx* c, const rpgpu_fetch_job* job, void* stream) {
+    if (!c || !job) return RPGPU_E_INVALID;
+    if (!job->d_totals || !job->d_ftotals || !job->d_out_part_offsets || !job->d_part_segments)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: missing argument");
+    if (job->n_partitions && (!job->d_requests || !job->d_parts))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: missing partition arrays");
+    if (job->n_segments && (!job->d_seg_offsets || !job->d_summaries))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: missing segment arrays");
+    if (job->batch_capacity && (!job->d_batches || !job->d_data))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: missing job outputs");
+    const int have_index = (job->d_index_states != nullptr) + (job->d_rel_offset != nullptr) + (job->d_position != nullptr);
+    if (have_index != 0 && have_index != 3)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: the entry index needs all three arrays");
+    if ((job->out_capacity && !job->d_out) || (job->out_batch_capacity && !job->d_out_batches))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: missing output buffer");
+    if (((uintptr_t)job->d_out & 15) != 0) return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: d_out must be 16-byte aligned");
+    // batch ordinals, output slots and copy pieces are counted in 32 bits
+    if (job->batch_capacity >= 0x7FFFFFFFull || job->n_segments > 0x7FFFFFFFu || job->n_partitions > 0x7FFFFFFFu ||
+        job->out_batch_capacity >= 0x7FFFFFFFull || job->out_capacity / kAppendPiece >= 0x7FFFFFFFull)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_fetch: capacity out of range");
+    hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    const uint64_t nb = job->batch_capacity, np = job->n_partitions;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t o = need; need += align_up(bytes, 256); return o; };
+    // bpos, bcnt and brec lie back to back: one memset zeroes the three
+    const size_t plan_bytes = align_up((nb + 1) * 8, 256);
+    const size_t o_bpos = take(plan_bytes), o_bcnt = take(plan_bytes), o_brec = take(plan_bytes);
+    const size_t o_bpart = take(nb * 4), o_sel = take(np * sizeof(FetchSel));
+    const size_t o_scan = take(scan_temp_bytes(nb) + 64);
+    need += 256;
+    if (int rc = grow(c, c->fws, need, s, "rpgpu_fetch workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->fws.as<uint8_t>();
+    FetchArgs a;
+    a.job = *job;
+    a.nb = nb;
+    a.bpos = (uint64_t*)(w + o_bpos);
+    a.bcnt = (uint64_t*)(w + o_bcnt);
+    a.brec = (uint64_t*)(w + o_brec);
+    a.bpart = (uint32_t*)(w + o_bpart);
+    a.sel = (FetchSel*)(w + o_sel);
+    const bool timed = c->timing;
+    auto mark = [&](int i) -> hipError_t {
+        if (!timed) return hipSuccess;
+        if (!c->fev[i]) {
+            hipError_t e = hipEventCreate(&c->fev[i]);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(c->fev[i], s);
+    };
+    c->fev_live = false;
+    HIPCHK(c, mark(0));
+    // k_fetch_select writes the returned batches only; the scans leave the
+    // totals at [nb], without batches these zeroes are the totals
+    HIPCHK(c, hipMemsetAsync(a.bpos, 0, 3 * plan_bytes, s));
+    HIPCHK(c, hipMemsetAsync(job->d_ftotals, 0, sizeof(rpgpu_fetch_totals), s));
+    if (np) HIPCHK(c, launch_fetch_select(a, s));
+    HIPCHK(c, mark(1));
+    if (nb) {
+        HIPCHK(c, scan_exclusive_u64(a.bpos, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+        HIPCHK(c, scan_exclusive_u64(a.bcnt, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+        HIPCHK(c, scan_exclusive_u64(a.brec, nb, w + o_scan, scan_temp_bytes(nb) + 64, s));
+    }
+    HIPCHK(c, launch_fetch_plan(a, s));
+    HIPCHK(c, mark(2));
+    if (nb && np) HIPCHK(c, launch_fetch_copy(a, c->cu_count, s));
+    HIPCHK(c, mark(3));
+    HIPCHK(c, mark(4));
+    c->fev_live = timed;
+    return scratch.release();
+}
+
+int rpgpu_fetch_timings(rpgpu_ctx* c, float* ms, int n) {
+    if (!c || !ms) return RPGPU_E_INVALID;
+    if (!c->fev_live) return fail(c, RPGPU_E_INVALID, "rpgpu_fetch_timings: no timed rpgpu_fetch");
+    HIPCHK(c, hipEventSynchronize(c->fev[4]));
+    float v[5] = {0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventElapsedTime(&v[0], c->fev[0], c->fev[4]));
+    for (int i = 1; i < 5; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->fev[i - 1], c->fev[i]));
+    for (int i = 0; i < n && i < 5; i++) ms[i] = v[i];
     return RPGPU_OK;
 }
 

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from ._lib import AppendJobC, CapacityC, CompactJobC, JobC, RpgpuError, check, load
+from ._lib import AppendJobC, CapacityC, CompactJobC, FetchJobC, JobC, RpgpuError, check, load
 
 
 def _torch():
@@ -146,6 +146,42 @@ class HostAppendResult:
     batches: np.ndarray
     summaries: np.ndarray
     sets: np.ndarray
+    totals: np.void
+
+
+@dataclass
+class FetchResult:
+    """Device outputs of Engine.fetch (rpgpu_fetch)."""
+    out: "object"               # uint8 tensor: the partitions' wire record sets back to back
+    out_part_offsets: "object"  # int64 tensor, n_partitions + 1
+    batches: "object"           # uint8 tensor viewed as abi.FETCH_BATCH on the host
+    parts: "object"             # uint8 tensor viewed as abi.FETCH_PART
+    ftotals: "object"           # uint8 tensor viewed as abi.FETCH_TOTALS
+    n_partitions: int
+
+    def totals_host(self):
+        return np.frombuffer(self.ftotals.cpu().numpy().tobytes(), dtype=abi.FETCH_TOTALS)[0]
+
+    def to_host(self):
+        t = self.totals_host()
+        ok = not t["overflow"]
+        nb = int(t["batches_out"]) if ok else 0
+        nby = int(t["bytes_out"]) if ok else 0
+        return HostFetchResult(
+            out=self.out[:nby].cpu().numpy(),
+            out_part_offsets=self.out_part_offsets.cpu().numpy().view(np.uint64),
+            batches=np.frombuffer(self.batches[: nb * abi.FETCH_BATCH.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.FETCH_BATCH),
+            parts=np.frombuffer(self.parts.cpu().numpy().tobytes(), dtype=abi.FETCH_PART)[: self.n_partitions],
+            totals=t)
+
+
+@dataclass
+class HostFetchResult:
+    out: np.ndarray
+    out_part_offsets: np.ndarray
+    batches: np.ndarray
+    parts: np.ndarray
     totals: np.void
 
 
@@ -592,6 +628,112 @@ class Engine:
             out_capacity = int(at_["out_capacity_needed"])
             out_batch_capacity = int(at_["out_batch_capacity_needed"])
         return res
+
+    @staticmethod
+    def fetch_request(start_offset: int, max_offset: int, max_bytes: int = (1 << 64) - 1, strict: bool = False,
+                      type_filter=None, first_timestamp=None):
+        """One abi.FETCH_REQUEST row: a storage::log_reader_config."""
+        flags = (abi.FETCH_STRICT_MAX_BYTES if strict else 0) | (abi.FETCH_TYPE_FILTER if type_filter is not None else 0)
+        flags |= abi.FETCH_FIRST_TIMESTAMP if first_timestamp is not None else 0
+        return (start_offset, max_offset, max_bytes, first_timestamp or 0, flags, type_filter or 0, (0, 0, 0))
+
+    def fetch(self, data, seg_offsets, out: DeviceResult, part_segments, requests, index=None, out_capacity: int = None,
+              out_batch_capacity: int = None, stream=None, sync: bool = True, out_buffer=None,
+              out_batch_buffer=None) -> "FetchResult":
+        """rpgpu_fetch: the log read of a Kafka fetch over a completed
+        disk-layout job `out` (at least JOB_CRC over `data`, a torch uint8
+        CUDA tensor).  Partition p is the job's segments [part_segments[p],
+        part_segments[p + 1]); requests holds one abi.FETCH_REQUEST per
+        partition (an array of that dtype, or rows as fetch_request() makes
+        them).  index: None, or the tensors Engine.segment_index returned for
+        this job: the reader then enters each segment at
+        segment_index::find_nearest(start).  Returns device tensors: every
+        partition's returned batches as a Kafka v2 record set, back to back;
+        .to_host() gives numpy views.  The capacities default to what always
+        fits (the source bytes plus 16; the source batch count); a call whose
+        capacity turns out too small is retried once with the sizes the
+        device reported (sync=False skips that check and the retry).
+        out_buffer / out_batch_buffer: uint8 CUDA tensors (the first 16-byte
+        aligned) of at least out_capacity bytes / out_batch_capacity entries
+        to write the first attempt into."""
+        torch = _torch()
+        dev = data.device
+        t = out.totals_host()
+        nb = int(min(t["n_batches"], out.batches.numel() // abi.BATCH_RESULT.itemsize))
+        nseg = out.n_segments
+        h_off = np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.uint64))
+        d_off = torch.from_numpy(h_off.view(np.int64)).to(dev)
+        ps = np.ascontiguousarray(np.asarray(part_segments, dtype=np.uint32))
+        npart = ps.size - 1
+        if npart < 0:
+            raise RpgpuError("fetch: part_segments needs n_partitions + 1 entries")
+        rq = np.zeros(max(npart, 1), dtype=abi.FETCH_REQUEST)
+        rq[:npart] = np.asarray(requests, dtype=abi.FETCH_REQUEST) if npart else rq[:0]
+        d_ps = torch.from_numpy(ps.view(np.int32).copy()).to(dev)
+        d_rq = torch.from_numpy(rq.view(np.uint8).copy()).to(dev)
+        if out_capacity is None:
+            out_capacity = int(h_off[-1]) + 16
+        if out_batch_capacity is None:
+            out_batch_capacity = nb
+        u8 = torch.uint8
+        part_off = torch.zeros(npart + 1, dtype=torch.int64, device=dev)
+        parts = torch.zeros(max(npart, 1) * abi.FETCH_PART.itemsize, dtype=u8, device=dev)
+        tot = torch.zeros(abi.FETCH_TOTALS.itemsize, dtype=u8, device=dev)
+        for attempt in range(2):
+            if out_buffer is not None and attempt == 0:
+                if out_buffer.numel() < out_capacity:
+                    raise RpgpuError("fetch: out_buffer smaller than out_capacity")
+                obuf = out_buffer
+            else:
+                obuf = torch.zeros(max(out_capacity, 16), dtype=u8, device=dev)
+            if out_batch_buffer is not None and attempt == 0:
+                if out_batch_buffer.numel() < out_batch_capacity * abi.FETCH_BATCH.itemsize:
+                    raise RpgpuError("fetch: out_batch_buffer smaller than out_batch_capacity")
+                obat = out_batch_buffer
+            else:
+                obat = torch.zeros(max(out_batch_capacity, 1) * abi.FETCH_BATCH.itemsize, dtype=u8, device=dev)
+            job = FetchJobC()
+            job.d_data = data.data_ptr()
+            job.d_seg_offsets = d_off.data_ptr()
+            job.n_segments = nseg
+            job.n_partitions = npart
+            job.d_batches = out.batches.data_ptr()
+            job.batch_capacity = nb
+            job.d_summaries = out.summaries.data_ptr()
+            job.d_totals = out.totals.data_ptr()
+            job.d_part_segments = d_ps.data_ptr()
+            job.d_requests = d_rq.data_ptr()
+            if index is not None:
+                job.d_index_states = index[0].data_ptr()
+                job.d_rel_offset = index[1].data_ptr()
+                job.d_position = index[3].data_ptr()
+            job.d_out = obuf.data_ptr()
+            job.out_capacity = out_capacity
+            job.d_out_part_offsets = part_off.data_ptr()
+            job.d_out_batches = obat.data_ptr()
+            job.out_batch_capacity = out_batch_capacity
+            job.d_parts = parts.data_ptr()
+            job.d_ftotals = tot.data_ptr()
+            s, finish = self._stream(dev, stream)
+            check(self.L.rpgpu_fetch(self.ctx, C.byref(job), C.c_void_p(s.cuda_stream)), self.ctx, "rpgpu_fetch")
+            finish(data, d_off, out.batches, out.summaries, out.totals, d_ps, d_rq, obuf, part_off, obat, parts, tot,
+                   *(index or ()))
+            res = FetchResult(obuf, part_off, obat, parts, tot, npart)
+            if not sync:
+                return res
+            s.synchronize()
+            ft = res.totals_host()
+            if not ft["overflow"] or attempt:
+                return res
+            out_capacity = int(ft["out_capacity_needed"])
+            out_batch_capacity = int(ft["out_batch_capacity_needed"])
+        return res
+
+    def fetch_timings(self):
+        """Device milliseconds of the last rpgpu_fetch run under set_timing()."""
+        ms = (C.c_float * 5)()
+        check(self.L.rpgpu_fetch_timings(self.ctx, ms, 5), self.ctx, "rpgpu_fetch_timings")
+        return {"total": ms[0], "select": ms[1], "scan_plan": ms[2], "copy": ms[3], "meta": ms[4]}
 
     def append_timings(self):
         """Device milliseconds of the last rpgpu_append_wire run under set_timing()."""

@@ -640,6 +640,135 @@ size_t rpgpu_compact_sizeof(int which);
 int rpgpu_compact_timings(rpgpu_ctx* ctx, float* ms, int n);
 
 /* ------------------------------------------------------------------------ */
+/* Recompression of compacted batches: storage::internal::compress_batch     */
+/* (storage/parser_utils.cc:82-120) as copy_data_segment_reducer::           */
+/* do_compaction calls it on every batch filter() returns                    */
+/* (storage/compaction_reducers.cc:223-258), and compress_batch_consumer     */
+/* (parser_utils.cc:62-80).  Device-resident: rpgpu_compact's outputs in,    */
+/* the on-disk compacted segments and the results of a validation job over   */
+/* them out.                                                                 */
+/* ------------------------------------------------------------------------ */
+/* rpgpu_recompress_job.codec: every batch gets its rpgpu_compact_batch.codec,
+ * do_compaction's `original` codec */
+#define RPGPU_RECOMPRESS_SOURCE_CODEC 0xFFFFFFFFu
+
+/* rpgpu_recompress_batch.flags */
+#define RPGPU_RECOMPRESS_F_COMPRESSED (1u << 0) /* LZ4 / snappy: compressed here, header restamped */
+#define RPGPU_RECOMPRESS_F_HOST (1u << 1)       /* gzip / zstd: copied uncompressed, the host's to finish with
+                                                   rpgpu_compress_batch */
+#define RPGPU_RECOMPRESS_F_BAD_CODEC (1u << 2)  /* codec value 5..7: copied uncompressed */
+#define RPGPU_RECOMPRESS_F_TOO_LARGE (1u << 3)  /* the compressed size bound (or a snappy fragment's bound, which
+                                                   snappy-java frames as int32) does not fit size_bytes: copied
+                                                   uncompressed */
+
+/* One entry per output batch, in output (= input) order.  32 bytes. */
+typedef struct rpgpu_recompress_batch {
+    uint64_t out_pos;         /* header position in d_out */
+    uint32_t in_batch;        /* ordinal of the batch in d_in_batches */
+    uint32_t payload_len;     /* bytes after the 61-byte header in d_out */
+    uint32_t in_payload_len;  /* the uncompressed payload's bytes */
+    uint32_t codec;           /* the codec the batch was to get: the job's, or the entry's with
+                                 RPGPU_RECOMPRESS_SOURCE_CODEC; RPGPU_CODEC_NONE for a batch below min_batch_bytes */
+    uint32_t flags;           /* RPGPU_RECOMPRESS_F_*; 0: copied verbatim (codec none, or below min_batch_bytes) */
+    uint32_t reserved;
+} rpgpu_recompress_batch;
+
+/* Whole call.  64 bytes. */
+typedef struct rpgpu_recompress_totals {
+    uint64_t batches_out;
+    uint64_t batches_compressed;         /* RPGPU_RECOMPRESS_F_COMPRESSED */
+    uint64_t batches_host;               /* RPGPU_RECOMPRESS_F_HOST */
+    uint64_t bytes_in;                   /* 61 + payload_len over the input batches */
+    uint64_t bytes_out;
+    uint64_t out_capacity_needed;        /* bytes_out + 16 */
+    uint64_t out_batch_capacity_needed;  /* batches_out */
+    uint32_t overflow;                   /* bit 0: out_capacity, bit 1: out_batch_capacity too small: nothing is
+                                            written to d_out / d_out_entries / d_out_batches, the sizes needed are
+                                            reported.  Bit 2: the source d_ctotals->overflow != 0, or the input
+                                            entries do not describe batches inside [0, in_capacity - 16): nothing
+                                            is written, every count is 0 and every segment offset 0 */
+    uint32_t reserved;
+} rpgpu_recompress_totals;
+
+/* All pointers are DEVICE pointers, caller-owned.  The first block is the
+ * outputs of a completed rpgpu_compact (same stream, or synchronised): every
+ * input batch is an uncompressed disk-layout batch, its stamped header at
+ * out_pos and payload_len bytes behind it. */
+typedef struct rpgpu_recompress_job {
+    const uint8_t* d_in;                 /* rpgpu_compact's d_out */
+    uint64_t in_capacity;                /* its out_capacity (with the 16 spare bytes): bounds the input bytes and
+                                            sizes scratch */
+    const uint64_t* d_in_seg_offsets;    /* n_segments + 1: rpgpu_compact's d_out_seg_offsets */
+    uint32_t n_segments;
+    uint32_t codec;                      /* RPGPU_RECOMPRESS_SOURCE_CODEC, or an rpgpu_codec value every batch gets
+                                            (compress_batch_consumer's _compression_type; 5..7: see the flags) */
+    const rpgpu_compact_batch* d_in_batches;
+    uint64_t in_batch_capacity;          /* rpgpu_compact's out_batch_capacity */
+    const rpgpu_compact_totals* d_ctotals; /* batches_out is the batch count, read on the device */
+    uint64_t min_batch_bytes;            /* a batch with 61 + payload_len below it is copied verbatim
+                                            (compress_batch_consumer's `>= _threshold`); 0: none */
+    uint64_t snappy_frag;                /* the iobuf fragment size of every snappy payload, as rpgpu_compress_batch's
+                                            frag (0: one fragment); a non-zero value below 4096 is invalid */
+    /* outputs */
+    uint8_t* d_out;                      /* the batches back to back, in input order; 16-byte aligned */
+    uint64_t out_capacity;               /* bytes, including 16 spare bytes past the last batch.  The sum over the
+                                            input batches of 61 + max(payload_len, rpgpu_compress_bound(codec,
+                                            payload_len, snappy_frag)), plus 16, is always enough: a copied batch
+                                            keeps its bytes; an LZ4 frame is at most 15 header bytes, a size word
+                                            and at most the block's own bytes per 64 KiB block (a block that does
+                                            not shrink is stored raw) and the end mark; a snappy-java payload is 16
+                                            header bytes and per fragment a length word and a RawCompress output of
+                                            at most snappy::MaxCompressedLength(fragment) -- the terms of
+                                            rpgpu_compress_bound */
+    uint64_t* d_out_seg_offsets;         /* n_segments + 1: segment s's output is [s, s + 1) */
+    rpgpu_recompress_batch* d_out_entries;
+    rpgpu_batch_result* d_out_batches;   /* one per output batch, in output order */
+    uint64_t out_batch_capacity;         /* of d_out_entries and of d_out_batches */
+    rpgpu_segment_summary* d_out_summaries; /* n_segments */
+    rpgpu_recompress_totals* d_rtotals;  /* one */
+} rpgpu_recompress_job;
+
+/* Per batch, by its effective codec (the job's, or the entry's):
+ *   LZ4, snappy   the payload becomes exactly what rpgpu_compress_batch
+ *                 returns for those bytes (snappy: over snappy_frag-byte
+ *                 fragments); the header is the input header with attrs |=
+ *                 codec, size_bytes = 61 + the compressed length, crc =
+ *                 crc_record_batch over the new header and payload, then
+ *                 header_crc (compress_batch + reset_size_checksum_metadata);
+ *                 every other field is unchanged.  The compressed form is
+ *                 kept even when it is larger, as the reference keeps it.
+ *   none, or 61 + payload_len < min_batch_bytes
+ *                 the batch's bytes verbatim.
+ *   gzip, zstd    the batch's bytes verbatim, still uncompressed (the log
+ *                 stays valid), flagged RPGPU_RECOMPRESS_F_HOST.
+ *   5..7          verbatim, RPGPU_RECOMPRESS_F_BAD_CODEC.
+ * LZ4 frames do not depend on the iobuf's fragmentation
+ * (lz4_frame_compressor.cc:69-113), so the reference's bytes are promised
+ * outright; snappy-java's are promised relative to snappy_frag.
+ *
+ * d_out_batches and d_out_summaries hold exactly what a disk-layout
+ * rpgpu_submit with RPGPU_JOB_CRC alone over d_out / d_out_seg_offsets
+ * reports (index_base = decoded_off = 0, decoded_len = payload_len for an
+ * uncompressed batch and 0 for a compressed one), so rpgpu_segment_index
+ * and rpgpu_fetch take them without another validation pass.
+ *
+ * Asynchronous on `stream`; never writes out of bounds: a capacity that is
+ * too small sets d_rtotals->overflow and reports the sizes needed.  NULL or
+ * inconsistent arguments return RPGPU_E_INVALID without touching a device. */
+int rpgpu_recompress(rpgpu_ctx* ctx, const rpgpu_recompress_job* job, void* stream);
+
+/* sizeof of the recompression structs as compiled into the library: 0 =
+ * rpgpu_recompress_batch, 1 = rpgpu_recompress_totals, 2 = rpgpu_batch_result,
+ * 3 = rpgpu_recompress_job (0 for any other value). */
+size_t rpgpu_recompress_sizeof(int which);
+
+/* Device time of the last timed rpgpu_recompress (rpgpu_set_timing), in
+ * milliseconds: 0 = whole call, 1 = plan, 2 = block compression, 3 = scans +
+ * layout, 4 = pack + copy, 5 = stamp + output metadata.  Synchronises on the
+ * call's last event. */
+int rpgpu_recompress_timings(rpgpu_ctx* ctx, float* ms, int n);
+
+/* ------------------------------------------------------------------------ */
 /* Produce path: validated Kafka v2 record sets -> the bytes the log         */
 /* receives (kafka_batch_adapter::adapt, kafka/protocol/                     */
 /* kafka_batch_adapter.cc:32-91, :126-188; the partition verdict of          */

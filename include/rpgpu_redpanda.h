@@ -947,12 +947,19 @@ struct compacted_segment {
     rpgpu_compact_segment stats{};
 };
 
-// Key compaction of one disk-layout segment on the device: rpgpu_submit
-// (CRC | PARSE | DECODE) then rpgpu_compact over its outputs.  Throws
-// std::runtime_error where the segment is not eligible (a batch fails crc,
-// decode or parse, or record offsets do not increase): the reference's path
-// throws or asserts there.
-inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::engine& e = rpgpu::engine::local()) {
+namespace detail {
+// rpgpu_compact's outputs while they are still on the device
+struct compact_outputs {
+    const rpgpu_compact_job& job;
+    const rpgpu_compact_totals& totals;
+    const std::vector<rpgpu_compact_batch>& batches;
+};
+
+// compact_segment (below); `after(compact_outputs, compacted_segment&)` runs
+// once an eligible segment's outputs are complete, before the device buffers
+// are released
+template <class After>
+inline compacted_segment compact_segment_then(const uint8_t* seg, size_t len, rpgpu::engine& e, After&& after) {
     rpgpu_ctx* c = e.ctx();
     rpgpu::dev_buffer d_data(e, len + 16), d_offs(e, 16);
     const uint64_t offs[2] = {0, (uint64_t)len};
@@ -1042,6 +1049,7 @@ inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::
                     "rpgpu_memcpy_d2h");
         if (words) e.check(rpgpu_memcpy_d2h(c, keep.data(), d_keep.get(), (size_t)words * 8, nullptr), "rpgpu_memcpy_d2h");
         e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+        if (res.stats.status == RPGPU_COMPACT_OK) after(compact_outputs{k, ct, ob}, res);
         break;
     }
     if (res.stats.status == RPGPU_COMPACT_NOT_CLEAN)
@@ -1054,6 +1062,161 @@ inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::
               (int64_t)((uint64_t)batches[records[i].batch].base_offset + (uint64_t)(int64_t)records[i].offset_delta));
     for (const auto& b : ob) res.codecs.push_back(static_cast<model::compression>(b.codec));
     return res;
+}
+}  // namespace detail
+
+// Key compaction of one disk-layout segment on the device: rpgpu_submit
+// (CRC | PARSE | DECODE) then rpgpu_compact over its outputs.  Throws
+// std::runtime_error where the segment is not eligible (a batch fails crc,
+// decode or parse, or record offsets do not increase): the reference's path
+// throws or asserts there.
+inline compacted_segment compact_segment(const uint8_t* seg, size_t len, rpgpu::engine& e = rpgpu::engine::local()) {
+    return detail::compact_segment_then(seg, len, e, [](const detail::compact_outputs&, compacted_segment&) {});
+}
+
+// do_compaction's compress_batch (rpgpu_recompress)
+struct recompress_options {
+    uint32_t codec = RPGPU_RECOMPRESS_SOURCE_CODEC;  // or a model::compression value for every batch
+    uint64_t min_batch_bytes = 0;                    // compress_batch_consumer's threshold (0: none)
+    uint64_t snappy_frag = 0;                        // the iobuf fragment size of the snappy payloads (0: one fragment)
+};
+
+// The segment self_compact_segment writes, and the index it builds beside it
+// (do_copy_segment_data's index_state: copy_data_segment_reducer feeds every
+// written batch to _idx.maybe_index).
+struct recompacted_segment {
+    std::vector<uint8_t> bytes;                   // the on-disk compacted segment
+    std::vector<int64_t> kept_offsets;            // compacted_offset_list: the surviving record offsets, ascending
+    std::vector<rpgpu_recompress_batch> batches;  // per output batch; positions and lengths are those in `bytes`
+    rpgpu_compact_segment stats{};
+    rpgpu_recompress_totals recompress{};         // the device call's (gzip / zstd batches still uncompressed)
+    index_state index;                            // base_offset = the first output batch's
+};
+
+// Key compaction of one segment through to its on-disk form, device-resident:
+// rpgpu_submit -> rpgpu_compact -> rpgpu_recompress -> rpgpu_segment_index
+// (segment_index::default_data_buffer_step), the compacted bytes copied out
+// once.  gzip / zstd batches (RPGPU_RECOMPRESS_F_HOST) are compressed on the
+// host with compress_batch and spliced in; the index is then rebuilt from the
+// final bytes (log_replayer::recover), since every position behind the first
+// such batch moved.  Throws like compact_segment.
+inline recompacted_segment compact_segment(const uint8_t* seg, size_t len, const recompress_options& opt,
+                                           rpgpu::engine& e = rpgpu::engine::local()) {
+    recompacted_segment out;
+    const size_t step = segment_index::default_data_buffer_step;
+    const compacted_segment cs = detail::compact_segment_then(
+      seg, len, e, [&](const detail::compact_outputs& co, compacted_segment& res) {
+          rpgpu_ctx* c = e.ctx();
+          const uint64_t nb = co.batches.size();
+          uint64_t out_cap = 16;
+          for (const auto& b : co.batches) {
+              const uint32_t codec = opt.codec == RPGPU_RECOMPRESS_SOURCE_CODEC ? b.codec : opt.codec;
+              out_cap += RPGPU_HEADER_SIZE +
+                         std::max<uint64_t>(b.payload_len, rpgpu_compress_bound((int)codec, b.payload_len, opt.snappy_frag));
+          }
+          rpgpu::dev_buffer d_out(e, out_cap), d_oso(e, 16), d_ent(e, (nb + 1) * sizeof(rpgpu_recompress_batch)),
+              d_rb(e, (nb + 1) * sizeof(rpgpu_batch_result)), d_sum(e, sizeof(rpgpu_segment_summary)),
+              d_rt(e, sizeof(rpgpu_recompress_totals));
+          rpgpu_recompress_job r{};
+          r.d_in = co.job.d_out;
+          r.in_capacity = co.job.out_capacity;
+          r.d_in_seg_offsets = co.job.d_out_seg_offsets;
+          r.n_segments = 1;
+          r.codec = opt.codec;
+          r.d_in_batches = co.job.d_out_batches;
+          r.in_batch_capacity = co.job.out_batch_capacity;
+          r.d_ctotals = co.job.d_ctotals;
+          r.min_batch_bytes = opt.min_batch_bytes;
+          r.snappy_frag = opt.snappy_frag;
+          r.d_out = (uint8_t*)d_out.get();
+          r.out_capacity = out_cap;
+          r.d_out_seg_offsets = (uint64_t*)d_oso.get();
+          r.d_out_entries = (rpgpu_recompress_batch*)d_ent.get();
+          r.d_out_batches = (rpgpu_batch_result*)d_rb.get();
+          r.out_batch_capacity = nb;
+          r.d_out_summaries = (rpgpu_segment_summary*)d_sum.get();
+          r.d_rtotals = (rpgpu_recompress_totals*)d_rt.get();
+          e.check(rpgpu_recompress(c, &r, nullptr), "rpgpu_recompress");
+          // the index over the device's own batch results: no second validation pass
+          rpgpu_index_state ist{};
+          ist.assert_batch = -1;
+          if (nb) std::memcpy(&ist.base_offset, res.bytes.data() + co.batches[0].out_pos + 8, 8);
+          rpgpu::dev_buffer d_ist(e, sizeof ist), d_ro(e, (nb + 1) * 4), d_tm(e, (nb + 1) * 4), d_pos(e, (nb + 1) * 8);
+          e.check(rpgpu_memcpy_h2d(c, d_ist.get(), &ist, sizeof ist, nullptr), "rpgpu_memcpy_h2d");
+          if (nb)
+              e.check(rpgpu_segment_index(c, r.d_out_batches, nb, r.d_out_summaries, 1, step,
+                                          (rpgpu_index_state*)d_ist.get(), (uint32_t*)d_ro.get(), (uint32_t*)d_tm.get(),
+                                          (uint64_t*)d_pos.get(), nullptr),
+                      "rpgpu_segment_index");
+          e.check(rpgpu_memcpy_d2h(c, &out.recompress, d_rt.get(), sizeof out.recompress, nullptr), "rpgpu_memcpy_d2h");
+          e.check(rpgpu_memcpy_d2h(c, &ist, d_ist.get(), sizeof ist, nullptr), "rpgpu_memcpy_d2h");
+          e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+          if (out.recompress.overflow) throw std::runtime_error("compact_segment: recompression output capacity");
+          out.bytes.resize((size_t)out.recompress.bytes_out);
+          out.batches.resize((size_t)out.recompress.batches_out);
+          std::vector<rpgpu_batch_result> rb(out.batches.size());
+          const size_t ne = (size_t)ist.n_entries, e0 = (size_t)ist.first_entry;
+          out.index.relative_offset_index.resize(ne);
+          out.index.relative_time_index.resize(ne);
+          out.index.position_index.resize(ne);
+          if (!out.bytes.empty())
+              e.check(rpgpu_memcpy_d2h(c, out.bytes.data(), d_out.get(), out.bytes.size(), nullptr), "rpgpu_memcpy_d2h");
+          if (!rb.empty()) {
+              e.check(rpgpu_memcpy_d2h(c, out.batches.data(), d_ent.get(), rb.size() * sizeof(rpgpu_recompress_batch), nullptr),
+                      "rpgpu_memcpy_d2h");
+              e.check(rpgpu_memcpy_d2h(c, rb.data(), d_rb.get(), rb.size() * sizeof(rpgpu_batch_result), nullptr),
+                      "rpgpu_memcpy_d2h");
+          }
+          if (ne) {
+              e.check(rpgpu_memcpy_d2h(c, out.index.relative_offset_index.data(), (uint32_t*)d_ro.get() + e0, ne * 4, nullptr),
+                      "rpgpu_memcpy_d2h");
+              e.check(rpgpu_memcpy_d2h(c, out.index.relative_time_index.data(), (uint32_t*)d_tm.get() + e0, ne * 4, nullptr),
+                      "rpgpu_memcpy_d2h");
+              e.check(rpgpu_memcpy_d2h(c, out.index.position_index.data(), (uint64_t*)d_pos.get() + e0, ne * 8, nullptr),
+                      "rpgpu_memcpy_d2h");
+          }
+          e.check(rpgpu_sync(c, nullptr), "rpgpu_sync");
+          if (ist.assert_batch >= 0) throw std::runtime_error("index_state::maybe_index: offset below base_offset");
+          out.index.base_offset = ist.base_offset;
+          out.index.max_offset = ist.max_offset;
+          out.index.base_timestamp = ist.base_timestamp;
+          out.index.max_timestamp = ist.max_timestamp;
+          if (!out.recompress.batches_host) return;
+          // the host's share: compress_batch per flagged batch, the segment reassembled
+          std::vector<uint8_t> fin;
+          fin.reserve(out.bytes.size());
+          for (size_t i = 0; i < out.batches.size(); i++) {
+              rpgpu_recompress_batch& g = out.batches[i];
+              const uint8_t* at = out.bytes.data() + g.out_pos;
+              const size_t pos = fin.size();
+              if (!(g.flags & RPGPU_RECOMPRESS_F_HOST)) {
+                  fin.insert(fin.end(), at, at + RPGPU_HEADER_SIZE + g.payload_len);
+              } else {
+                  auto [h, payload] = compress_batch(static_cast<model::compression>(g.codec),
+                                                     model::record_batch_header::from(rb[i]),
+                                                     rpgpu::iobuf(at + RPGPU_HEADER_SIZE, g.payload_len), e);
+                  uint8_t hb[RPGPU_HEADER_SIZE];
+                  std::memcpy(hb, at, sizeof hb);  // base_offset .. record_count stay; attrs, size and the crcs change
+                  const int16_t attrs = h.attrs.value();
+                  std::memcpy(hb + 0, &h.header_crc, 4);
+                  std::memcpy(hb + 4, &h.size_bytes, 4);
+                  std::memcpy(hb + 17, &h.crc, 4);
+                  std::memcpy(hb + 21, &attrs, 2);
+                  fin.insert(fin.end(), hb, hb + sizeof hb);
+                  fin.insert(fin.end(), payload.data(), payload.data() + payload.size_bytes());
+                  g.payload_len = (uint32_t)payload.size_bytes();
+                  g.flags |= RPGPU_RECOMPRESS_F_COMPRESSED;
+              }
+              g.out_pos = pos;
+          }
+          out.bytes.swap(fin);
+          index_state idx;
+          log_replayer::recover(out.bytes.data(), out.bytes.size(), ist.base_offset, idx, step, e);
+          out.index = std::move(idx);
+      });
+    out.kept_offsets = cs.kept_offsets;
+    out.stats = cs.stats;
+    return out;
 }
 
 }  // namespace internal

@@ -54,6 +54,19 @@ class CompactJobC(C.Structure):
     ]
 
 
+class RecompressJobC(C.Structure):
+    """rpgpu_recompress_job (include/rpgpu.h)."""
+    _fields_ = [
+        ("d_in", C.c_void_p), ("in_capacity", C.c_uint64), ("d_in_seg_offsets", C.c_void_p),
+        ("n_segments", C.c_uint32), ("codec", C.c_uint32),
+        ("d_in_batches", C.c_void_p), ("in_batch_capacity", C.c_uint64), ("d_ctotals", C.c_void_p),
+        ("min_batch_bytes", C.c_uint64), ("snappy_frag", C.c_uint64),
+        ("d_out", C.c_void_p), ("out_capacity", C.c_uint64), ("d_out_seg_offsets", C.c_void_p),
+        ("d_out_entries", C.c_void_p), ("d_out_batches", C.c_void_p), ("out_batch_capacity", C.c_uint64),
+        ("d_out_summaries", C.c_void_p), ("d_rtotals", C.c_void_p),
+    ]
+
+
 class AppendJobC(C.Structure):
     """rpgpu_append_job (include/rpgpu.h)."""
     _fields_ = [
@@ -154,6 +167,9 @@ def load():
         "rpgpu_compact": (i32, [vp, C.POINTER(CompactJobC), vp]),
         "rpgpu_compact_sizeof": (sz, [i32]),
         "rpgpu_compact_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
+        "rpgpu_recompress": (i32, [vp, C.POINTER(RecompressJobC), vp]),
+        "rpgpu_recompress_sizeof": (sz, [i32]),
+        "rpgpu_recompress_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
         "rpgpu_append_wire": (i32, [vp, C.POINTER(AppendJobC), vp]),
         "rpgpu_append_sizeof": (sz, [i32]),
         "rpgpu_append_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
@@ -188,6 +204,6 @@ def crc32c(data, crc: int = 0) -> int:
     return load().rpgpu_crc32c_extend(crc, a.ctypes.data_as(C.c_void_p), a.nbytes)
 
 
-__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "AppendJobC", "FetchJobC",
+__all__ = ["load", "check", "crc32c", "JobC", "CapacityC", "CompactJobC", "RecompressJobC", "AppendJobC", "FetchJobC",
            "FetchRequestC", "RpgpuError", "abi",
            "exported_symbols_from_header"]

@@ -124,6 +124,24 @@ COMPACT_SEGMENT_COMPARE_FIELDS = [n for n in COMPACT_SEGMENT.names if n != "rese
 # key_compare_mismatches counts work (it depends on the insertion order), not a result
 COMPACT_TOTALS_COMPARE_FIELDS = [n for n in COMPACT_TOTALS.names if n not in ("reserved", "key_compare_mismatches")]
 
+# rpgpu_recompress (include/rpgpu.h): recompression of compacted batches
+RECOMPRESS_SOURCE_CODEC = 0xFFFFFFFF
+RECOMPRESS_F_COMPRESSED, RECOMPRESS_F_HOST, RECOMPRESS_F_BAD_CODEC, RECOMPRESS_F_TOO_LARGE = 1 << 0, 1 << 1, 1 << 2, 1 << 3
+
+RECOMPRESS_BATCH = np.dtype([
+    ("out_pos", "<u8"), ("in_batch", "<u4"), ("payload_len", "<u4"), ("in_payload_len", "<u4"), ("codec", "<u4"),
+    ("flags", "<u4"), ("reserved", "<u4"),
+])
+assert RECOMPRESS_BATCH.itemsize == 32
+RECOMPRESS_TOTALS = np.dtype([
+    ("batches_out", "<u8"), ("batches_compressed", "<u8"), ("batches_host", "<u8"), ("bytes_in", "<u8"),
+    ("bytes_out", "<u8"), ("out_capacity_needed", "<u8"), ("out_batch_capacity_needed", "<u8"), ("overflow", "<u4"),
+    ("reserved", "<u4"),
+])
+assert RECOMPRESS_TOTALS.itemsize == 64
+RECOMPRESS_BATCH_COMPARE_FIELDS = [n for n in RECOMPRESS_BATCH.names if n != "reserved"]
+RECOMPRESS_TOTALS_COMPARE_FIELDS = [n for n in RECOMPRESS_TOTALS.names if n != "reserved"]
+
 # rpgpu_append_wire (include/rpgpu.h): produce-path append of wire record sets
 APPEND_OK, APPEND_CORRUPT_MESSAGE, APPEND_INVALID_RECORD, APPEND_MALFORMED, APPEND_SOURCE_OVERFLOW = 0, 1, 2, 3, 4
 APPEND_ALL_BATCHES = 1 << 0

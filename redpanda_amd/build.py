@@ -20,7 +20,7 @@ OUT = os.path.join(HERE, "librpgpu.so")
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("RPGPU_ARCH", "gfx950")
 
-HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip", "rp_fetch.hip",
+HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip", "rp_fetch.hip", "rp_recompress.hip",
                "rp_runtime.hip"]
 CXX_SOURCES = ["rp_hostcodec.cpp"]
 
@@ -128,6 +128,23 @@ def build_compact_test(force: bool = False) -> str:
         _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, COMPACT_SRC, "-o", COMPACT_BIN, "-L", HERE, "-l:librpgpu.so",
               "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
     return COMPACT_BIN
+
+
+RECOMPRESS_SRC = os.path.join(ROOT, "tests", "cpp", "recompress_main.cpp")
+RECOMPRESS_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "recompress_test")
+
+
+def build_recompress_test(force: bool = False) -> str:
+    """Host driver of storage::internal::compact_segment with
+    recompress_options (include/rpgpu_redpanda.h), linked like the surfaces
+    driver."""
+    lib = build()
+    hdrs = [os.path.join(INC, "rpgpu.h"), os.path.join(INC, "rpgpu_redpanda.h")]
+    if force or _stale(RECOMPRESS_BIN, [RECOMPRESS_SRC, lib] + hdrs):
+        os.makedirs(os.path.dirname(RECOMPRESS_BIN), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, RECOMPRESS_SRC, "-o", RECOMPRESS_BIN, "-L", HERE,
+              "-l:librpgpu.so", "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
+    return RECOMPRESS_BIN
 
 
 APPEND_SRC = os.path.join(ROOT, "tests", "cpp", "append_main.cpp")

@@ -33,11 +33,13 @@ namespace {
 
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 
-// 4 bytes at s + i (s = a block of a fragment staged 16-byte aligned; reads
-// up to 7 bytes past i)
+// 4 bytes at s + i, from the two aligned dwords around that address: any
+// alignment of s (a staged fragment starts 16-byte aligned; a payload inside a
+// log starts anywhere).  Reads up to 3 bytes before s + i and 7 past it.
 DEV uint32_t g32(const uint8_t* __restrict__ s, uint32_t i) {
-    const uint32_t* w = (const uint32_t*)(s + (i & ~3u));
-    return __builtin_amdgcn_alignbyte(w[1], w[0], i & 3);
+    const uintptr_t a = (uintptr_t)(s + i);
+    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
+    return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(a & 3));
 }
 
 DEV void put16(lds_u16* T, uint32_t h, uint32_t v) {
@@ -264,6 +266,7 @@ emit_remainder:
 template <uint32_t kCodec>
 __global__ __launch_bounds__(64) void k_compress_blocks(const uint8_t* __restrict__ in, const CompBlock* __restrict__ blocks,
                                                         uint32_t nb, uint8_t* __restrict__ scratch,
+                                                        const uint64_t* __restrict__ slot_off,
                                                         uint32_t* __restrict__ sizes) {
     __shared__ uint16_t table[kCodec == RPGPU_CODEC_SNAPPY ? 16384 : (1u << kLzHashLog)];
     lds_u16* T = (lds_u16*)table;
@@ -274,7 +277,7 @@ __global__ __launch_bounds__(64) void k_compress_blocks(const uint8_t* __restric
     const uint64_t src = uni64(blocks[b].src);
     const uint32_t n = uni32(blocks[b].n);
     const uint8_t* s = in + src;
-    uint8_t* d = scratch + (uint64_t)b * kCompSlot;
+    uint8_t* d = scratch + (slot_off ? uni64(slot_off[b]) : (uint64_t)b * kCompSlot);
     uint32_t tsize = 1u << kLzHashLog;
     int shift = 0;
     if (kCodec == RPGPU_CODEC_SNAPPY) {
@@ -290,34 +293,8 @@ __global__ __launch_bounds__(64) void k_compress_blocks(const uint8_t* __restric
     if (lane() == 0) sizes[b] = r;
 }
 
-// XXH32 of at most 15 bytes (the LZ4F header checksum)
-DEV uint32_t xxh32_small(const uint8_t* p, uint32_t len) {
-    constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
-    uint32_t h = P5 + len;
-    uint32_t i = 0;
-    for (; i + 4 <= len; i += 4) {
-        const uint32_t v = p[i] | (p[i + 1] << 8) | (p[i + 2] << 16) | ((uint32_t)p[i + 3] << 24);
-        h += v * P3;
-        h = ((h << 17) | (h >> 15)) * P4;
-    }
-    for (; i < len; i++) {
-        h += p[i] * P5;
-        h = ((h << 11) | (h >> 21)) * P1;
-    }
-    h ^= h >> 15;
-    h *= P2;
-    h ^= h >> 13;
-    h *= P3;
-    h ^= h >> 16;
-    return h;
-}
-
-DEV void put_le32(uint8_t* d, uint64_t at, uint32_t v) {
-    if (lane() == 0)
-        for (int i = 0; i < 4; i++) d[at + i] = (uint8_t)(v >> (8 * i));
-}
-
-// one wave per payload: the frame from the block outputs
+// one wave per payload: the frame from the block outputs (wave_write_frame,
+// rp_device.h)
 __global__ __launch_bounds__(64) void k_compress_pack(const uint8_t* __restrict__ in, const CompPayload* __restrict__ pay,
                                                       uint32_t np, const CompBlock* __restrict__ blocks,
                                                       const uint8_t* __restrict__ scratch,
@@ -325,80 +302,10 @@ __global__ __launch_bounds__(64) void k_compress_pack(const uint8_t* __restrict_
                                                       uint64_t* __restrict__ out_len) {
     const uint32_t p = blockIdx.x;
     if (p >= np) return;
-    const uint32_t l = lane();
     const uint64_t n = uni64(pay[p].n), base = uni64(pay[p].out);
     const uint32_t first = uni32(pay[p].first), nbk = uni32(pay[p].nblocks), codec = uni32(pay[p].codec);
-    uint8_t* d = out + base;
-    uint64_t o = 0;
-    if (codec == RPGPU_CODEC_LZ4) {
-        // LZ4F_compressBegin: magic, FLG (version 01, independent blocks,
-        // content size when non-zero), BD (max64KB), content size, HC
-        uint8_t h[15];
-        h[0] = 0x04; h[1] = 0x22; h[2] = 0x4D; h[3] = 0x18;
-        h[4] = (uint8_t)(0x60 | (n ? 0x08 : 0));
-        h[5] = 0x40;
-        uint32_t hl = 6;
-        if (n) {
-            for (int i = 0; i < 8; i++) h[6 + i] = (uint8_t)(n >> (8 * i));
-            hl = 14;
-        }
-        h[hl] = (uint8_t)((xxh32_small(h + 4, hl - 4) >> 8) & 0xFF);
-        hl++;
-        if (l == 0)
-            for (uint32_t i = 0; i < hl; i++) d[i] = h[i];
-        o = hl;
-        for (uint32_t k = 0; k < nbk; k++) {
-            const uint32_t b = first + k;
-            const uint32_t c = uni32(sizes[b]), bn = uni32(blocks[b].n);
-            if (c == 0) {  // LZ4F_makeBlock: does not fit -> raw block
-                put_le32(d, o, bn | 0x80000000u);
-                wave_copy(d + o + 4, in + uni64(blocks[b].src), bn);
-                o += 4 + bn;
-            } else {
-                put_le32(d, o, c);
-                wave_copy(d + o + 4, scratch + (uint64_t)b * kCompSlot, c);
-                o += 4 + c;
-            }
-        }
-        put_le32(d, o, 0);  // end mark
-        o += 4;
-    } else {
-        // snappy-java header: magic, version 1, min version 1 (LE, as the
-        // reference appends them)
-        if (l == 0) {
-            const uint8_t hdr[16] = {0x82, 'S', 'N', 'A', 'P', 'P', 'Y', 0, 1, 0, 0, 0, 1, 0, 0, 0};
-            for (int i = 0; i < 16; i++) d[i] = hdr[i];
-        }
-        o = 16;
-        for (uint32_t k = 0; k < nbk;) {
-            // a fragment: its blocks, then BE32 length + RawCompress output
-            const uint32_t b0 = first + k;
-            const uint32_t fb = uni32(blocks[b0].frag_blocks);
-            const uint32_t flen = uni32(blocks[b0].frag_len);
-            uint32_t vl = 1;
-            for (uint32_t v = flen; v >= 128; v >>= 7) vl++;
-            uint32_t tot = vl;
-            for (uint32_t j = 0; j < fb; j++) tot += uni32(sizes[b0 + j]);
-            if (l == 0) {
-                d[o] = (uint8_t)(tot >> 24);
-                d[o + 1] = (uint8_t)(tot >> 16);
-                d[o + 2] = (uint8_t)(tot >> 8);
-                d[o + 3] = (uint8_t)tot;
-                uint32_t v = flen;
-                uint64_t q = o + 4;
-                while (v >= 128) { d[q++] = (uint8_t)(v | 128); v >>= 7; }
-                d[q] = (uint8_t)v;
-            }
-            o += 4 + vl;
-            for (uint32_t j = 0; j < fb; j++) {
-                const uint32_t c = uni32(sizes[b0 + j]);
-                wave_copy(d + o, scratch + (uint64_t)(b0 + j) * kCompSlot, c);
-                o += c;
-            }
-            k += fb;
-        }
-    }
-    if (l == 0) out_len[p] = o;
+    const uint64_t o = wave_write_frame(out + base, in, n, first, nbk, codec, blocks, scratch, nullptr, sizes);
+    if (lane() == 0) out_len[p] = o;
 }
 
 }  // namespace
@@ -406,10 +313,23 @@ __global__ __launch_bounds__(64) void k_compress_pack(const uint8_t* __restrict_
 hipError_t launch_compress(const uint8_t* in, const CompBlock* blocks, uint32_t nb, const CompPayload* pay, uint32_t np,
                            uint8_t* scratch, uint32_t* sizes, uint8_t* out, uint64_t* out_len, hipStream_t s) {
     if (nb) {
-        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_LZ4>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch, sizes);
-        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_SNAPPY>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch, sizes);
+        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_LZ4>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch, nullptr,
+                           sizes);
+        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_SNAPPY>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch,
+                           nullptr, sizes);
     }
     if (np) hipLaunchKernelGGL(k_compress_pack, dim3(np), dim3(64), 0, s, in, pay, np, blocks, scratch, sizes, out, out_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_compress_blocks(const uint8_t* in, const CompBlock* blocks, uint32_t nb, uint8_t* scratch,
+                                  const uint64_t* slot_off, uint32_t* sizes, bool lz4, bool snappy, hipStream_t s) {
+    if (nb && lz4)
+        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_LZ4>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch, slot_off,
+                           sizes);
+    if (nb && snappy)
+        hipLaunchKernelGGL(k_compress_blocks<RPGPU_CODEC_SNAPPY>, dim3(nb), dim3(64), 0, s, in, blocks, nb, scratch,
+                           slot_off, sizes);
     return hipGetLastError();
 }
 

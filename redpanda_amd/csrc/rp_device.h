@@ -420,6 +420,115 @@ HD uint64_t decode_capacity_raw(int codec, const uint8_t* s, uint64_t n) {
 
 
 // ---------------------------------------------------------------------------
+// compressor::compress framing over the block kernels' outputs
+// (rp_compress.hip), shared by k_compress_pack (one frame per payload slot)
+// and k_recompress_pack (rp_recompress.hip: frames inside a log).  Block b's
+// compressed bytes lie at scratch + slot_off[b] (slot_off null: b * kCompSlot),
+// sizes[b] of them; an LZ4 block with sizes[b] == 0 did not fit and is stored
+// raw from in + blocks[b].src (LZ4F_makeBlock).
+// ---------------------------------------------------------------------------
+DEV const uint8_t* comp_slot(const uint8_t* scratch, const uint64_t* slot_off, uint32_t b) {
+    return scratch + (slot_off ? slot_off[b] : (uint64_t)b * kCompSlot);
+}
+// LZ4F_compressBegin: magic, FLG (version 01, independent blocks, content
+// size when non-zero), BD (max64KB), content size, HC; returns its length
+HD uint32_t lz4f_header(uint8_t (&h)[15], uint64_t n) {
+    h[0] = 0x04; h[1] = 0x22; h[2] = 0x4D; h[3] = 0x18;
+    h[4] = (uint8_t)(0x60 | (n ? 0x08 : 0));
+    h[5] = 0x40;
+    uint32_t hl = 6;
+    if (n) {
+        for (int i = 0; i < 8; i++) h[6 + i] = (uint8_t)(n >> (8 * i));
+        hl = 14;
+    }
+    h[hl] = (uint8_t)((xxh32_small(h + 4, hl - 4) >> 8) & 0xFF);
+    return hl + 1;
+}
+HD uint32_t varint32_len(uint32_t v) {
+    uint32_t vl = 1;
+    for (; v >= 128; v >>= 7) vl++;
+    return vl;
+}
+// the frame's length, one thread
+DEV uint64_t frame_bytes(uint64_t n, uint32_t first, uint32_t nbk, uint32_t codec, const CompBlock* __restrict__ blocks,
+                         const uint32_t* __restrict__ sizes) {
+    uint64_t o;
+    if (codec == RPGPU_CODEC_LZ4) {
+        o = n ? 15 : 7;
+        for (uint32_t k = 0; k < nbk; k++) {
+            const uint32_t c = sizes[first + k];
+            o += 4 + (c ? c : blocks[first + k].n);
+        }
+        return o + 4;
+    }
+    o = 16;
+    for (uint32_t k = 0; k < nbk; k++) {
+        if (blocks[first + k].frag_blocks) o += 4 + varint32_len(blocks[first + k].frag_len);
+        o += sizes[first + k];
+    }
+    return o;
+}
+// the frame at d, one wave; returns its length (frame_bytes)
+DEV uint64_t wave_write_frame(uint8_t* __restrict__ d, const uint8_t* __restrict__ in, uint64_t n, uint32_t first,
+                              uint32_t nbk, uint32_t codec, const CompBlock* __restrict__ blocks,
+                              const uint8_t* __restrict__ scratch, const uint64_t* __restrict__ slot_off,
+                              const uint32_t* __restrict__ sizes) {
+    const uint32_t l = lane();
+    uint64_t o = 0;
+    if (codec == RPGPU_CODEC_LZ4) {
+        uint8_t h[15];
+        const uint32_t hl = lz4f_header(h, n);
+        if (l == 0)
+            for (uint32_t i = 0; i < hl; i++) d[i] = h[i];
+        o = hl;
+        for (uint32_t k = 0; k < nbk; k++) {
+            const uint32_t b = first + k;
+            const uint32_t c = uni32(sizes[b]), bn = uni32(blocks[b].n);
+            const uint32_t word = c ? c : (bn | 0x80000000u);  // LZ4F_makeBlock: does not fit -> raw block
+            if (l < 4) d[o + l] = (uint8_t)(word >> (8 * l));
+            wave_copy_lines(d + o + 4, c ? comp_slot(scratch, slot_off, b) : in + uni64(blocks[b].src), c ? c : bn, l);
+            o += 4 + (c ? c : bn);
+        }
+        if (l < 4) d[o + l] = 0;  // end mark
+        return o + 4;
+    }
+    // snappy-java header: magic, version 1, min version 1 (LE, as the
+    // reference appends them)
+    if (l < 16) {
+        const uint8_t hdr[16] = {0x82, 'S', 'N', 'A', 'P', 'P', 'Y', 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        d[l] = hdr[l];
+    }
+    o = 16;
+    for (uint32_t k = 0; k < nbk;) {
+        // a fragment: its blocks, then BE32 length + RawCompress output
+        const uint32_t b0 = first + k;
+        const uint32_t fb = uni32(blocks[b0].frag_blocks);
+        const uint32_t flen = uni32(blocks[b0].frag_len);
+        const uint32_t vl = varint32_len(flen);
+        uint32_t tot = vl;
+        for (uint32_t j = 0; j < fb; j++) tot += uni32(sizes[b0 + j]);
+        if (l == 0) {
+            d[o] = (uint8_t)(tot >> 24);
+            d[o + 1] = (uint8_t)(tot >> 16);
+            d[o + 2] = (uint8_t)(tot >> 8);
+            d[o + 3] = (uint8_t)tot;
+            uint32_t v = flen;
+            uint64_t q = o + 4;
+            while (v >= 128) { d[q++] = (uint8_t)(v | 128); v >>= 7; }
+            d[q] = (uint8_t)v;
+        }
+        o += 4 + vl;
+        for (uint32_t j = 0; j < fb; j++) {
+            const uint32_t c = uni32(sizes[b0 + j]);
+            wave_copy_lines(d + o, comp_slot(scratch, slot_off, b0 + j), c, l);
+            o += c;
+        }
+        k += fb ? fb : 1;
+    }
+    return o;
+}
+
+// ---------------------------------------------------------------------------
 // GF(2) arithmetic modulo the reflected CRC32C polynomial (zlib's multmodp /
 // x2nmodp scheme; bit 31 is x^0): merging partial CRCs (k_crc_combine) and
 // the pieces of a decoded payload (k_decode_finish).  x has order 2^31 - 1

@@ -491,7 +491,7 @@ constexpr uint32_t kCompSlot = 76800;
 constexpr uint64_t kSplitMin = 256u << 10;
 constexpr uint32_t kSplitParts = 16;
 struct CompBlock {
-    uint64_t src;                    // staged input offset (a fragment starts 16-byte aligned; 8 readable bytes past it)
+    uint64_t src;                    // input offset of the block (any alignment; 8 readable bytes past the block)
     uint32_t n, codec;               // block bytes (<= 65536), RPGPU_CODEC_LZ4 / _SNAPPY
     uint32_t frag_len, frag_blocks;  // snappy: on a fragment's first block, the fragment's bytes and blocks
 };
@@ -501,6 +501,11 @@ struct CompPayload {
 };
 hipError_t launch_compress(const uint8_t* in, const CompBlock* blocks, uint32_t nb, const CompPayload* pay, uint32_t np,
                            uint8_t* scratch, uint32_t* sizes, uint8_t* out, uint64_t* out_len, hipStream_t s);
+// the block kernels alone, over a block array that may hold fewer than nb
+// blocks (the rest zeroed: codec 0, their waves leave); block b compresses into
+// scratch + slot_off[b] (slot_off null: b * kCompSlot)
+hipError_t launch_compress_blocks(const uint8_t* in, const CompBlock* blocks, uint32_t nb, uint8_t* scratch,
+                                  const uint64_t* slot_off, uint32_t* sizes, bool lz4, bool snappy, hipStream_t s);
 hipError_t launch_uncompress_many(const UncItem* items, uint32_t count, const uint8_t* in, uint64_t in_total,
                                   uint8_t* out, int64_t* res, hipStream_t s);
 hipError_t launch_finalize(const DeviceJob& j, hipStream_t s);
@@ -610,5 +615,44 @@ struct FetchArgs {
 hipError_t launch_fetch_select(const FetchArgs& a, hipStream_t s);  // bpos / bcnt / brec zeroed before
 hipError_t launch_fetch_plan(const FetchArgs& a, hipStream_t s);    // after the scans: parts, offsets, totals
 hipError_t launch_fetch_copy(const FetchArgs& a, uint32_t cus, hipStream_t s);  // payloads, headers, d_out_batches
+
+// rp_recompress.hip: recompression of compacted batches (rpgpu_recompress).
+// Workspace arrays are context scratch; nb bounds the input batch count, the
+// block array and the block scratch are sized from the input capacities
+// (recompress_block_cap / recompress_scratch_cap).
+// RecompressArgs::mode[b]: the effective codec in the low byte, then
+constexpr uint32_t kRcCompress = 1u << 8;  // compressed here (its blocks are planned)
+struct RecompressArgs {
+    rpgpu_recompress_job job;
+    uint64_t nb;              // job.in_batch_capacity
+    uint32_t* mode;           // nb: effective codec | kRcCompress | RPGPU_RECOMPRESS_F_* << 16
+    uint64_t* bblk;           // nb + 1: 64 KiB blocks per input batch -> exclusive scan (the batch's first block)
+    uint64_t* bscr;           // nb + 1: block scratch bytes per input batch -> exclusive scan
+    uint64_t* bpos;           // nb + 1: output bytes per input batch -> exclusive scan
+    uint64_t* bcnt;           // nb + 1: low half 1 per batch, high half its pack pieces -> exclusive scan
+    uint32_t* clen;           // nb: output payload bytes per batch
+    CompBlock* blocks;        // block_cap, zeroed per call
+    uint64_t block_cap;
+    uint64_t* slot_off;       // block_cap: where each block compresses to in `scratch`
+    uint32_t* sizes;          // block_cap: the block kernels' output sizes
+    uint8_t* scratch;
+    uint64_t scratch_cap;
+    uint64_t* spos;           // nb: rpgpu_stamp positions of the compressed batches
+    uint32_t* splen;          // nb: their payload lengths
+    uint32_t* counters;       // the words RecompressCounter names
+};
+enum RecompressCounter : uint32_t {
+    kRcStampCount = 0,   // compressed batches to stamp: k_recompress_pack lists them; k_stamp (its d_n)
+    kRcStampCursor = 1,  // k_stamp's claim cursor
+    kRcBadInput = 2,     // an input entry lies outside in_capacity, or the plan outgrew the block array / scratch
+    kRcCount = 3
+};
+// what the block array and the block scratch must hold for any input within the capacities
+uint64_t recompress_block_cap(uint64_t in_capacity, uint64_t in_batch_capacity, uint64_t snappy_frag);
+uint64_t recompress_scratch_cap(uint64_t in_capacity, uint64_t block_cap);
+hipError_t launch_recompress_plan(const RecompressArgs& a, void* scan_tmp, size_t scan_bytes, hipStream_t s);
+hipError_t launch_recompress_layout(const RecompressArgs& a, void* scan_tmp, size_t scan_bytes, hipStream_t s);
+hipError_t launch_recompress_pack(const RecompressArgs& a, uint32_t cus, hipStream_t s);
+hipError_t launch_recompress_meta(const RecompressArgs& a, hipStream_t s);  // after the stamp
 
 }  // namespace rp

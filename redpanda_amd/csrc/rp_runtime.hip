@@ -152,6 +152,12 @@ struct rpgpu_ctx {
     Buf fws;
     hipEvent_t fev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool fev_live = false;
+    // rpgpu_recompress workspace (per-batch plan, the block array, the block
+    // kernels' scratch, scan temporaries, the stamp list); its stage events
+    // (rpgpu_set_timing)
+    Buf rws;
+    hipEvent_t rev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool rev_live = false;
     // k_lz_exec parse records (kRecsPerLane per lane of each resident wave),
     // allocated on the first decode job
     Buf seqs;
@@ -460,7 +466,7 @@ int rpgpu_destroy(rpgpu_ctx* c) {
         if (sd->join_ev) (void)hipEventDestroy(sd->join_ev);
     }
     if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
-    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->fws, &c->seqs, &c->pool, &c->fpool,
+    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->fws, &c->rws, &c->seqs, &c->pool, &c->fpool,
                    &c->sth, &c->std_, &c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h,
                    &c->hc_small, &c->gz_pool, &c->gzs_pool})
         b->release();
@@ -477,6 +483,8 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     for (hipEvent_t e : c->aev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->fev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->rev)
         if (e) hipEventDestroy(e);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     for (auto& set : c->ev_sets)
@@ -1481,6 +1489,123 @@ int rpgpu_compact_timings(rpgpu_ctx* c, float* ms, int n) {
     float v[6] = {0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipEventElapsedTime(&v[0], c->cev[0], c->cev[5]));
     for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->cev[i - 1], c->cev[i]));
+    for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
+    return RPGPU_OK;
+}
+
+// Recompression of a completed rpgpu_compact's batches (kernels in
+// rp_recompress.hip; the block kernels are rp_compress.hip's).
+size_t rpgpu_recompress_sizeof(int which) {
+    switch (which) {
+    case 0: return sizeof(rpgpu_recompress_batch);
+    case 1: return sizeof(rpgpu_recompress_totals);
+    case 2: return sizeof(rpgpu_batch_result);
+    case 3: return sizeof(rpgpu_recompress_job);
+    default: return 0;
+    }
+}
+
+int rpgpu_recompress(rpgpu_ctx* c, const rpgpu_recompress_job* job, void* stream) {
+    if (!c || !job) return RPGPU_E_INVALID;
+    if (!job->d_ctotals || !job->d_rtotals || !job->d_in_seg_offsets || !job->d_out_seg_offsets)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: missing argument");
+    if (job->n_segments && !job->d_out_summaries) return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: missing segment arrays");
+    if (job->in_batch_capacity && (!job->d_in_batches || !job->d_in))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: missing compaction outputs");
+    if ((job->out_capacity && !job->d_out) || (job->out_batch_capacity && (!job->d_out_entries || !job->d_out_batches)))
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: missing output buffer");
+    if (((uintptr_t)job->d_out & 15) != 0) return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: d_out must be 16-byte aligned");
+    if (job->codec != RPGPU_RECOMPRESS_SOURCE_CODEC && job->codec > 7)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: codec is neither an rpgpu_codec value nor SOURCE_CODEC");
+    // smaller fragments would unbound the block count the scratch is sized for
+    if (job->snappy_frag && job->snappy_frag < 4096)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: snappy_frag below 4096");
+    const uint64_t nb = job->in_batch_capacity, nseg = job->n_segments;
+    const uint64_t block_cap = recompress_block_cap(job->in_capacity, nb, job->snappy_frag);
+    // batch ordinals, block ordinals and pack pieces are counted in 32 bits
+    if (nb >= 0x7FFFFFFFull || job->out_batch_capacity >= 0x7FFFFFFFull || nseg > 0x7FFFFFFFu || block_cap >= 0x7FFFFFFFull)
+        return fail(c, RPGPU_E_INVALID, "rpgpu_recompress: capacity out of range");
+    hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    const uint64_t scratch_cap = recompress_scratch_cap(job->in_capacity, block_cap);
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t o = need; need += align_up(bytes, 256); return o; };
+    // bblk, bscr, bpos and bcnt lie back to back: one memset zeroes the four
+    const size_t plan_bytes = align_up((nb + 1) * 8, 256);
+    const size_t o_bblk = take(plan_bytes), o_bscr = take(plan_bytes), o_bpos = take(plan_bytes), o_bcnt = take(plan_bytes);
+    const size_t o_mode = take(nb * 4), o_clen = take(nb * 4), o_spos = take(nb * 8), o_splen = take(nb * 4);
+    const size_t o_blocks = take(block_cap * sizeof(CompBlock)), o_slot = take(block_cap * 8), o_sizes = take(block_cap * 4);
+    const size_t o_scan = take(scan_temp_bytes(nb) + 64), o_cnt = take(256), o_scr = take(scratch_cap + 16);
+    need += 256;
+    if (int rc = grow(c, c->rws, need, s, "rpgpu_recompress workspace")) return rc;
+    ScratchScope scratch(c, s);
+    if (int rc = scratch.acquired()) return rc;
+    uint8_t* w = c->rws.as<uint8_t>();
+    RecompressArgs a;
+    a.job = *job;
+    a.nb = nb;
+    a.mode = (uint32_t*)(w + o_mode);
+    a.bblk = (uint64_t*)(w + o_bblk);
+    a.bscr = (uint64_t*)(w + o_bscr);
+    a.bpos = (uint64_t*)(w + o_bpos);
+    a.bcnt = (uint64_t*)(w + o_bcnt);
+    a.clen = (uint32_t*)(w + o_clen);
+    a.blocks = (CompBlock*)(w + o_blocks);
+    a.block_cap = block_cap;
+    a.slot_off = (uint64_t*)(w + o_slot);
+    a.sizes = (uint32_t*)(w + o_sizes);
+    a.scratch = w + o_scr;
+    a.scratch_cap = scratch_cap;
+    a.spos = (uint64_t*)(w + o_spos);
+    a.splen = (uint32_t*)(w + o_splen);
+    a.counters = (uint32_t*)(w + o_cnt);
+    const bool timed = c->timing;
+    auto mark = [&](int i) -> hipError_t {
+        if (!timed) return hipSuccess;
+        if (!c->rev[i]) {
+            hipError_t e = hipEventCreate(&c->rev[i]);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(c->rev[i], s);
+    };
+    c->rev_live = false;
+    HIPCHK(c, mark(0));
+    // the scans leave the totals at [nb]; without batches these zeroes are the totals
+    HIPCHK(c, hipMemsetAsync(a.bblk, 0, 4 * plan_bytes, s));
+    HIPCHK(c, hipMemsetAsync(a.counters, 0, 256, s));
+    HIPCHK(c, hipMemsetAsync(job->d_rtotals, 0, sizeof(rpgpu_recompress_totals), s));
+    // the block kernels run over the whole array: a block the plan does not fill has codec 0
+    HIPCHK(c, hipMemsetAsync(a.blocks, 0, block_cap * sizeof(CompBlock), s));
+    if (nb) HIPCHK(c, launch_recompress_plan(a, w + o_scan, scan_temp_bytes(nb) + 64, s));
+    HIPCHK(c, mark(1));
+    if (nb) {
+        const bool any = job->codec == RPGPU_RECOMPRESS_SOURCE_CODEC;
+        HIPCHK(c, launch_compress_blocks(job->d_in, a.blocks, (uint32_t)block_cap, a.scratch, a.slot_off, a.sizes,
+                                         any || job->codec == RPGPU_CODEC_LZ4, any || job->codec == RPGPU_CODEC_SNAPPY, s));
+    }
+    HIPCHK(c, mark(2));
+    HIPCHK(c, launch_recompress_layout(a, w + o_scan, scan_temp_bytes(nb) + 64, s));
+    HIPCHK(c, mark(3));
+    if (nb) HIPCHK(c, launch_recompress_pack(a, c->cu_count, s));
+    HIPCHK(c, mark(4));
+    // compress_batch's reset_size_checksum_metadata, then header_crc
+    const uint64_t nstamp = std::min<uint64_t>(nb, job->out_batch_capacity);
+    if (nstamp && job->codec != RPGPU_CODEC_NONE)
+        HIPCHK(c, launch_stamp(job->d_out, a.spos, a.splen, nullptr, 0, (uint32_t)nstamp, RPGPU_STAMP_CRC, c->d_tables,
+                               a.counters + kRcStampCursor, c->cu_count, s, a.counters + kRcStampCount));
+    if (nb) HIPCHK(c, launch_recompress_meta(a, s));
+    HIPCHK(c, mark(5));
+    c->rev_live = timed;
+    return scratch.release();
+}
+
+int rpgpu_recompress_timings(rpgpu_ctx* c, float* ms, int n) {
+    if (!c || !ms) return RPGPU_E_INVALID;
+    if (!c->rev_live) return fail(c, RPGPU_E_INVALID, "rpgpu_recompress_timings: no timed rpgpu_recompress");
+    HIPCHK(c, hipEventSynchronize(c->rev[5]));
+    float v[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventElapsedTime(&v[0], c->rev[0], c->rev[5]));
+    for (int i = 1; i < 6; i++) HIPCHK(c, hipEventElapsedTime(&v[i], c->rev[i - 1], c->rev[i]));
     for (int i = 0; i < n && i < 6; i++) ms[i] = v[i];
     return RPGPU_OK;
 }

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from ._lib import AppendJobC, CapacityC, CompactJobC, FetchJobC, JobC, RpgpuError, check, load
+from ._lib import AppendJobC, CapacityC, CompactJobC, FetchJobC, JobC, RecompressJobC, RpgpuError, check, load
 
 
 def _torch():
@@ -68,6 +68,7 @@ class CompactResult:
     totals: "object"
     n_segments: int
     n_records: int
+    out_capacity: int = None   # the out_capacity of the call (None: out's size)
 
     def totals_host(self):
         return np.frombuffer(self.totals.cpu().numpy().tobytes(), dtype=abi.COMPACT_TOTALS)[0]
@@ -94,6 +95,57 @@ class HostCompactResult:
     out_seg_offsets: np.ndarray
     batches: np.ndarray
     segments: np.ndarray
+    totals: np.void
+
+
+@dataclass
+class RecompressResult:
+    """Device outputs of Engine.recompress (rpgpu_recompress).  `batches`,
+    `summaries`, `n_segments` and totals_host() have DeviceResult's shape, so
+    Engine.segment_index takes a RecompressResult where it takes a disk-layout
+    job's outputs."""
+    out: "object"              # uint8 tensor: the recompressed segments back to back
+    out_seg_offsets: "object"  # int64 tensor, n_segments + 1
+    entries: "object"          # uint8 tensor viewed as abi.RECOMPRESS_BATCH on the host
+    batches: "object"          # uint8 tensor viewed as abi.BATCH_RESULT
+    summaries: "object"        # uint8 tensor viewed as abi.SEGMENT_SUMMARY
+    rtotals: "object"          # uint8 tensor viewed as abi.RECOMPRESS_TOTALS
+    n_segments: int
+
+    def recompress_totals_host(self):
+        return np.frombuffer(self.rtotals.cpu().numpy().tobytes(), dtype=abi.RECOMPRESS_TOTALS)[0]
+
+    def totals_host(self):
+        """The rpgpu_job_totals a RPGPU_JOB_CRC disk-layout job over the output reports."""
+        r = self.recompress_totals_host()
+        t = np.zeros(1, dtype=abi.JOB_TOTALS)[0]
+        nb = 0 if r["overflow"] else int(r["batches_out"])
+        t["n_batches"] = t["batch_capacity_needed"] = nb
+        return t
+
+    def to_host(self):
+        t = self.recompress_totals_host()
+        ok = not t["overflow"]
+        nb = int(t["batches_out"]) if ok else 0
+        nby = int(t["bytes_out"]) if ok else 0
+        return HostRecompressResult(
+            out=self.out[:nby].cpu().numpy(),
+            out_seg_offsets=self.out_seg_offsets.cpu().numpy().view(np.uint64),
+            entries=np.frombuffer(self.entries[: nb * abi.RECOMPRESS_BATCH.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.RECOMPRESS_BATCH),
+            batches=np.frombuffer(self.batches[: nb * abi.BATCH_RESULT.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.BATCH_RESULT),
+            summaries=np.frombuffer(self.summaries.cpu().numpy().tobytes(), dtype=abi.SEGMENT_SUMMARY)[: self.n_segments],
+            totals=t)
+
+
+@dataclass
+class HostRecompressResult:
+    out: np.ndarray
+    out_seg_offsets: np.ndarray
+    entries: np.ndarray
+    batches: np.ndarray
+    summaries: np.ndarray
     totals: np.void
 
 
@@ -533,7 +585,7 @@ class Engine:
             check(self.L.rpgpu_compact(self.ctx, C.byref(job), C.c_void_p(s.cuda_stream)), self.ctx, "rpgpu_compact")
             finish(data, d_off, out.batches, out.records, out.decoded, out.summaries, out.totals, keep, obuf, seg_off,
                    obat, segs, tot)
-            res = CompactResult(keep, obuf, seg_off, obat, segs, tot, nseg, nr)
+            res = CompactResult(keep, obuf, seg_off, obat, segs, tot, nseg, nr, out_capacity)
             if not sync:
                 return res
             s.synchronize()
@@ -543,6 +595,75 @@ class Engine:
             out_capacity = int(ct["out_capacity_needed"])
             out_batch_capacity = int(ct["out_batch_capacity_needed"])
         return res
+
+    def recompress(self, compact_result: "CompactResult", codec: int = abi.RECOMPRESS_SOURCE_CODEC,
+                   min_batch_bytes: int = 0, snappy_frag: int = 0, out_capacity: int = None, stream=None,
+                   out_batch_capacity: int = None, out_buffer=None) -> "RecompressResult":
+        """rpgpu_recompress: the batches of a completed Engine.compact
+        compressed again on the device (do_compaction's compress_batch): LZ4
+        and snappy batches become what compress_batch gives (snappy over
+        snappy_frag-byte fragments), headers restamped; gzip / zstd ones stay
+        uncompressed, flagged abi.RECOMPRESS_F_HOST for the host to finish.
+        codec: abi.RECOMPRESS_SOURCE_CODEC (each batch its source codec) or
+        one codec for every batch; min_batch_bytes: smaller batches pass
+        through.  Returns device tensors (the segments, and the batch results
+        and summaries a JOB_CRC job over them reports); .to_host() gives
+        numpy views.  The capacities default to what always fits.
+        out_buffer: a 16-byte aligned uint8 CUDA tensor of at least
+        out_capacity bytes to write into."""
+        torch = _torch()
+        cr = compact_result
+        dev = cr.out.device
+        nseg = cr.n_segments
+        in_cap = int(cr.out_capacity) if cr.out_capacity is not None else cr.out.numel()
+        in_bcap = cr.batches.numel() // abi.COMPACT_BATCH.itemsize
+        if out_capacity is None or out_batch_capacity is None:
+            ct = cr.totals_host()
+            nb = 0 if ct["overflow"] else int(min(ct["batches_out"], in_bcap))
+            if out_batch_capacity is None:
+                out_batch_capacity = nb
+            if out_capacity is None:
+                b = np.frombuffer(cr.batches[: nb * abi.COMPACT_BATCH.itemsize].cpu().numpy().tobytes(),
+                                  dtype=abi.COMPACT_BATCH)
+                out_capacity = 16
+                for n, c in zip(b["payload_len"].tolist(), b["codec"].tolist()):
+                    c = c if codec == abi.RECOMPRESS_SOURCE_CODEC else codec
+                    out_capacity += abi.HEADER_SIZE + max(n, self.L.rpgpu_compress_bound(c, n, snappy_frag))
+        u8 = torch.uint8
+        if out_buffer is not None:
+            if out_buffer.numel() < out_capacity:
+                raise RpgpuError("recompress: out_buffer smaller than out_capacity")
+            obuf = out_buffer
+        else:
+            obuf = torch.zeros(max(out_capacity, 16), dtype=u8, device=dev)
+        seg_off = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+        oent = torch.zeros(max(out_batch_capacity, 1) * abi.RECOMPRESS_BATCH.itemsize, dtype=u8, device=dev)
+        obat = torch.zeros(max(out_batch_capacity, 1) * abi.BATCH_RESULT.itemsize, dtype=u8, device=dev)
+        sums = torch.zeros(max(nseg, 1) * abi.SEGMENT_SUMMARY.itemsize, dtype=u8, device=dev)
+        tot = torch.zeros(abi.RECOMPRESS_TOTALS.itemsize, dtype=u8, device=dev)
+        job = RecompressJobC()
+        job.d_in = cr.out.data_ptr()
+        job.in_capacity = in_cap
+        job.d_in_seg_offsets = cr.out_seg_offsets.data_ptr()
+        job.n_segments = nseg
+        job.codec = codec
+        job.d_in_batches = cr.batches.data_ptr()
+        job.in_batch_capacity = in_bcap
+        job.d_ctotals = cr.totals.data_ptr()
+        job.min_batch_bytes = min_batch_bytes
+        job.snappy_frag = snappy_frag
+        job.d_out = obuf.data_ptr()
+        job.out_capacity = out_capacity
+        job.d_out_seg_offsets = seg_off.data_ptr()
+        job.d_out_entries = oent.data_ptr()
+        job.d_out_batches = obat.data_ptr()
+        job.out_batch_capacity = out_batch_capacity
+        job.d_out_summaries = sums.data_ptr()
+        job.d_rtotals = tot.data_ptr()
+        s, finish = self._stream(dev, stream)
+        check(self.L.rpgpu_recompress(self.ctx, C.byref(job), C.c_void_p(s.cuda_stream)), self.ctx, "rpgpu_recompress")
+        finish(cr.out, cr.out_seg_offsets, cr.batches, cr.totals, obuf, seg_off, oent, obat, sums, tot)
+        return RecompressResult(obuf, seg_off, oent, obat, sums, tot, nseg)
 
     def append_wire(self, data, seg_offsets, out: DeviceResult, next_offsets, append_times=None,
                     all_batches: bool = False, stream=None, out_capacity: int = None, out_batch_capacity: int = None,
@@ -740,6 +861,13 @@ class Engine:
         ms = (C.c_float * 6)()
         check(self.L.rpgpu_append_timings(self.ctx, ms, 6), self.ctx, "rpgpu_append_timings")
         return {"total": ms[0], "verdict_sizes": ms[1], "scan_plan": ms[2], "copy": ms[3], "stamp": ms[4], "meta": ms[5]}
+
+    def recompress_timings(self):
+        """Device milliseconds of the last rpgpu_recompress run under set_timing()."""
+        ms = (C.c_float * 6)()
+        check(self.L.rpgpu_recompress_timings(self.ctx, ms, 6), self.ctx, "rpgpu_recompress_timings")
+        return {"total": ms[0], "plan": ms[1], "compress": ms[2], "scan_layout": ms[3], "pack": ms[4],
+                "stamp_meta": ms[5]}
 
     def compact_timings(self):
         """Device milliseconds of the last rpgpu_compact run under set_timing()."""

@@ -363,6 +363,20 @@ def compress(codec: int, data: bytes, frag: int = 0) -> bytes:
     return out[:n].tobytes()
 
 
+def lz4_compress_block(data: bytes, cap: int = None) -> bytes:
+    """rpo_lz4_compress_block: one LZ4 block into `cap` bytes (default: room
+    for any input, so no output-limit exit fires); b"" when it does not fit."""
+    L = lib()
+    L.rpo_lz4_compress_block.restype = C.c_int
+    L.rpo_lz4_compress_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    src = np.frombuffer(bytes(data) + b"\0" * 8, dtype=np.uint8)
+    room = len(data) + len(data) // 255 + 64
+    cap = room if cap is None else cap
+    out = np.zeros(max(room, cap) + 16, np.uint8)
+    n = L.rpo_lz4_compress_block(src.ctypes.data, len(data), out.ctypes.data, cap)
+    return out[:n].tobytes()
+
+
 def ref_compress(codec: int, data: bytes, frag: int = 0):
     """The same through the reference's codec libraries (oracle/_ref), or
     None when the harness is absent."""

@@ -21,6 +21,7 @@ import pytest
 from redpanda_amd import abi
 from tests import batchgen as BG
 from tests import compaction_ref as CR
+from tests import compress_edges as CE
 from tests import recompress_ref as RR
 from tests import test_compaction as TC
 
@@ -282,6 +283,126 @@ def test_gpu_edge_sizes(engine, oracle, codec, frag):
     assert grew[len(EDGE_SIZES):].all(), "random bytes: the compressed form is larger and is kept"
     assert_closure(engine, oracle, got, ref, pays, parse=False)
     assert_index(engine, oracle, dev, ref)
+
+
+# One case per LZ4 output-limit exit and the exact-fit pair (raw blocks are
+# copied from where the payload lies in the log, unstaged), and the cases whose
+# match ends at lane 63 / 0 of wave_count's second and third step, by a
+# mismatch and by the end of the block, for both codecs.
+ALIGN_CASES = ["lz4_exit1_literal_run", "lz4_exit2_match_length", "lz4_exit3_last_literals", "lz4_raw_at_n",
+               "lz4_fits_n_minus_1", "lz4_match_67", "lz4_match_68", "lz4_match_132", "lz4_mlimit_run_137",
+               "lz4_mlimit_run_138", "snappy_copy_67", "snappy_copy_68", "snappy_copy_132", "snappy_end_run_132",
+               "snappy_end_run_133"]
+_aligned = {}
+
+
+def aligned_layout():
+    """Every ALIGN_CASES payload 16 times, each behind a filler batch of 0..15
+    payload bytes chosen so that the payload starts at residue r = 0..15 mod 16
+    of the log: (cref, payloads, [(case, r, batch ordinal)])."""
+    if not _aligned:
+        edge = dict(CE.cases())
+        rng = np.random.default_rng(0xA119)
+        pays, where, pos = [], [], 0
+        for name in ALIGN_CASES:
+            for r in range(16):
+                f = (r - (pos + 2 * abi.HEADER_SIZE)) % 16
+                pays += [rng.integers(0, 256, f, dtype=np.uint8).tobytes(), edge[name]]
+                where.append((name, r, len(pays) - 1))
+                pos += 2 * abi.HEADER_SIZE + f + len(edge[name])
+        third = len(pays) // 3 // 2 * 2
+        cref = laid_out(pays, [abi.CODEC_NONE] * len(pays), seg_counts=[third, third, len(pays) - 2 * third])
+        _aligned.update(cref=cref, pays=pays, where=where)
+    return _aligned["cref"], _aligned["pays"], _aligned["where"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("codec,frag", [(abi.CODEC_LZ4, 0), (abi.CODEC_SNAPPY, 0), (abi.CODEC_SNAPPY, 4097)])
+def test_gpu_payload_alignments(engine, oracle, codec, frag):
+    """The block compressors read a payload where it lies in the log (g32 from
+    the absolute address) and raw LZ4 blocks are copied from there: every
+    residue mod 16 of the payload's first byte in the device buffer, for the
+    edge payloads of ALIGN_CASES."""
+    cref, pays, where = aligned_layout()
+    dcomp = to_device(cref)
+    base = dcomp.out.data_ptr()
+    assert base % 16 == 0
+    seen = {}
+    for name, r, b in where:
+        start = base + int(cref.batches[b]["out_pos"]) + abi.HEADER_SIZE
+        assert start % 16 == r and int(cref.batches[b - 1]["payload_len"]) < 16
+        seen.setdefault(name, set()).add(start % 16)
+    assert seen == {name: set(range(16)) for name in ALIGN_CASES}
+    ref = RR.recompress(cref, codec=codec, snappy_frag=frag)
+    got, dev = run_device(engine, dcomp, codec=codec, snappy_frag=frag)
+    assert int(got.totals["overflow"]) == 0
+    assert_model_parity(got, ref)
+    assert np.all(got.entries["flags"] == abi.RECOMPRESS_F_COMPRESSED)
+    if codec == abi.CODEC_LZ4:  # the exits' blocks are stored raw: the frame is the payload and 23 bytes
+        for name, r, b in where:
+            if name.startswith("lz4_exit") or name == "lz4_raw_at_n":
+                assert int(got.entries[b]["payload_len"]) == len(pays[b]) + 23, (name, r)
+    assert_closure(engine, oracle, got, ref, pays, parse=False)
+    assert_index(engine, oracle, dev, ref)
+
+
+def scale_layout(cu):
+    """cu * 32 + 307 batches of at most 32 payload bytes (none / LZ4 / snappy
+    by turns, one gzip), three uncompressed ones of 65535, 65536 and
+    3 * 65536 + 5 bytes, over 300 segments of which every ninth is empty."""
+    n_tiny = cu * 32 + 307
+    rng = np.random.default_rng(0x5CA1E)
+    pays, codecs = [], []
+    for i in range(n_tiny):
+        n = int(rng.integers(0, 33))
+        pays.append(bytes([i & 255]) * n if i % 5 == 0 else rng.integers(0, 256, n, dtype=np.uint8).tobytes())
+        codecs.append((abi.CODEC_NONE, abi.CODEC_LZ4, abi.CODEC_SNAPPY)[i % 3])
+    codecs[1000] = abi.CODEC_GZIP
+    big = {97: 65535, n_tiny // 2: 65536, n_tiny - 40: 3 * 65536 + 5}
+    for at, size in sorted(big.items()):
+        pays.insert(at, rng.integers(0, 256, size - abi.HEADER_SIZE, dtype=np.uint8).tobytes())
+        codecs.insert(at, abi.CODEC_NONE)
+    nb, nseg = len(pays), 300
+    full = [s for s in range(nseg) if s % 9 != 4]
+    seg_counts = [0] * nseg
+    for s in full:
+        seg_counts[s] = nb // len(full)
+    seg_counts[full[-1]] += nb - sum(seg_counts)
+    assert sum(seg_counts) == nb and seg_counts.count(0) > 30 and nseg > 256
+    return laid_out(pays, codecs, seg_counts=seg_counts), pays, codecs
+
+
+@pytest.mark.gpu
+def test_gpu_scale(engine, oracle):
+    """One call past every single-block limit of the recompress kernels: more
+    batches than one 256-thread block of the thread-per-batch kernels, more
+    than 256 segments (some empty) for k_recompress_layout, more pack pieces
+    than k_recompress_pack's grid has waves (cu_count * 32: its grid-stride
+    loop), and copied batches of 65535, 65536 (one piece) and 3 * 65536 + 5
+    bytes (four pieces).  The codecs come from the entries."""
+    import torch
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cref, pays, codecs = scale_layout(cu)
+    nb = len(pays)
+    ref = RR.recompress(cref)
+    pieces = sum(1 if int(e["flags"]) & abi.RECOMPRESS_F_COMPRESSED else -(-(abi.HEADER_SIZE + int(e["payload_len"])) // 65536)
+                 for e in ref.entries)
+    assert pieces > cu * 32 and pieces == nb + 3
+    got, dev = run_device(engine, to_device(cref))
+    assert int(got.totals["overflow"]) == 0
+    assert_model_parity(got, ref)
+    assert int(got.totals["batches_host"]) == 1
+    assert int(got.totals["batches_compressed"]) == sum(1 for c in codecs if c in (abi.CODEC_LZ4, abi.CODEC_SNAPPY))
+    copied = 0
+    for e in got.entries:
+        if not int(e["flags"]) & abi.RECOMPRESS_F_COMPRESSED:
+            s = cref.batches[int(e["in_batch"])]
+            n = abi.HEADER_SIZE + int(s["payload_len"])
+            assert got.out[int(e["out_pos"]):int(e["out_pos"]) + n].tobytes() == \
+                cref.out[int(s["out_pos"]):int(s["out_pos"]) + n].tobytes(), int(e["in_batch"])
+            copied += 1
+    assert copied == sum(1 for c in codecs if c in (abi.CODEC_NONE, abi.CODEC_GZIP))
+    assert_index(engine, oracle, dev, ref, steps=(1,))
 
 
 _chain = {}

@@ -441,9 +441,27 @@ size_t rpgpu_compress_bound(int codec, size_t n, size_t frag);
  * RPGPU_CODEC_NONE (the reference throws "nothing to compress").  gzip and
  * zstd run on the host, the reference's loops over zlib / libzstd
  * (gzip_compressor.cc:126-161, stream_zstd.cc:84-104; RPGPU_E_UNSUPPORTED
- * when the library cannot be loaded). */
+ * when the library cannot be loaded).  With rpgpu_set_device_gzip on (and a
+ * non-NULL ctx), gzip payloads are staged and compressed on the device in the
+ * same round trip, over frag[i]-byte fragments: the same bytes, statuses and
+ * sizes as the host path gives with zlib 1.2.11. */
 int rpgpu_compress_batch(rpgpu_ctx* ctx, uint32_t n, const int* codecs, const void* const* in, const size_t* in_len,
                          const size_t* frag, void* const* out, const size_t* cap, size_t* out_len, int* status);
+
+/* gzip compression on the device (off by default; off, every call behaves as
+ * without it): gzip_compressor::compress (gzip_compressor.cc:126-161) --
+ * deflateInit2(Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15 + 16, 8,
+ * Z_DEFAULT_STRATEGY), one deflate(Z_NO_FLUSH) per fragment, Z_FINISH -- with
+ * the bytes of zlib 1.2.11, one lane per payload (k_deflate).  It applies to
+ * rpgpu_compress_batch and to rpgpu_recompress (see there).  A payload whose deflateBound, n + (n >> 12) +
+ * (n >> 14) + (n >> 25) + 25, plus 61 does not fit int32 stays on the host. */
+int rpgpu_set_device_gzip(rpgpu_ctx* ctx, int enable);
+/* Device milliseconds of k_deflate in the last rpgpu_compress_batch that ran
+ * gzip payloads on the device under rpgpu_set_timing (HIP events on the
+ * call's stream); RPGPU_E_INVALID when there was none. */
+int rpgpu_gzip_device_ms(rpgpu_ctx* ctx, float* ms);
+/* *n = gzip payloads compressed on the device by this context so far */
+int rpgpu_gzip_device_payloads(rpgpu_ctx* ctx, uint64_t* n);
 
 /* ------------------------------------------------------------------------ */
 /* Host segment path (log_replayer over files, storage/log_replayer.cc:       */
@@ -653,13 +671,14 @@ int rpgpu_compact_timings(rpgpu_ctx* ctx, float* ms, int n);
 #define RPGPU_RECOMPRESS_SOURCE_CODEC 0xFFFFFFFFu
 
 /* rpgpu_recompress_batch.flags */
-#define RPGPU_RECOMPRESS_F_COMPRESSED (1u << 0) /* LZ4 / snappy: compressed here, header restamped */
-#define RPGPU_RECOMPRESS_F_HOST (1u << 1)       /* gzip / zstd: copied uncompressed, the host's to finish with
-                                                   rpgpu_compress_batch */
+#define RPGPU_RECOMPRESS_F_COMPRESSED (1u << 0) /* LZ4 / snappy (gzip with rpgpu_set_device_gzip): compressed here,
+                                                   header restamped */
+#define RPGPU_RECOMPRESS_F_HOST (1u << 1)       /* zstd (gzip without rpgpu_set_device_gzip): copied uncompressed,
+                                                   the host's to finish with rpgpu_compress_batch */
 #define RPGPU_RECOMPRESS_F_BAD_CODEC (1u << 2)  /* codec value 5..7: copied uncompressed */
 #define RPGPU_RECOMPRESS_F_TOO_LARGE (1u << 3)  /* the compressed size bound (or a snappy fragment's bound, which
-                                                   snappy-java frames as int32) does not fit size_bytes: copied
-                                                   uncompressed */
+                                                   snappy-java frames as int32; for device gzip, deflateBound)
+                                                   does not fit size_bytes: copied uncompressed */
 
 /* One entry per output batch, in output (= input) order.  32 bytes. */
 typedef struct rpgpu_recompress_batch {
@@ -677,7 +696,7 @@ typedef struct rpgpu_recompress_batch {
 typedef struct rpgpu_recompress_totals {
     uint64_t batches_out;
     uint64_t batches_compressed;         /* RPGPU_RECOMPRESS_F_COMPRESSED */
-    uint64_t batches_host;               /* RPGPU_RECOMPRESS_F_HOST */
+    uint64_t batches_host;               /* RPGPU_RECOMPRESS_F_HOST (zstd batches only with rpgpu_set_device_gzip) */
     uint64_t bytes_in;                   /* 61 + payload_len over the input batches */
     uint64_t bytes_out;
     uint64_t out_capacity_needed;        /* bytes_out + 16 */
@@ -719,7 +738,10 @@ typedef struct rpgpu_recompress_job {
                                             not shrink is stored raw) and the end mark; a snappy-java payload is 16
                                             header bytes and per fragment a length word and a RawCompress output of
                                             at most snappy::MaxCompressedLength(fragment) -- the terms of
-                                            rpgpu_compress_bound */
+                                            rpgpu_compress_bound; a gzip payload compressed here
+                                            (rpgpu_set_device_gzip) is at most deflateBound, payload_len +
+                                            (payload_len >> 12) + (payload_len >> 14) + (payload_len >> 25) + 25,
+                                            which rpgpu_compress_bound(RPGPU_CODEC_GZIP, ...) exceeds */
     uint64_t* d_out_seg_offsets;         /* n_segments + 1: segment s's output is [s, s + 1) */
     rpgpu_recompress_batch* d_out_entries;
     rpgpu_batch_result* d_out_batches;   /* one per output batch, in output order */
@@ -741,6 +763,19 @@ typedef struct rpgpu_recompress_job {
  *                 the batch's bytes verbatim.
  *   gzip, zstd    the batch's bytes verbatim, still uncompressed (the log
  *                 stays valid), flagged RPGPU_RECOMPRESS_F_HOST.
+ *   gzip, with rpgpu_set_device_gzip on
+ *                 compressed where it lies, as LZ4 above: the payload becomes
+ *                 what rpgpu_compress_batch returns for those bytes fed as
+ *                 ONE fragment (frag 0), RPGPU_RECOMPRESS_F_COMPRESSED.  The
+ *                 iobuf fragments of a rewritten payload are not known here;
+ *                 zlib 1.2.11's output did not depend on the fragmentation in
+ *                 any of 1800 fragmentations of 300 inputs tried (nor in this
+ *                 project's tests), but that is observed, not proven, so the
+ *                 reference's bytes are promised relative to one fragment, as
+ *                 snappy's are relative to snappy_frag.  A payload whose
+ *                 deflateBound plus 61 does not fit int32 is copied
+ *                 uncompressed, RPGPU_RECOMPRESS_F_TOO_LARGE.  batches_host
+ *                 then counts zstd batches only.
  *   5..7          verbatim, RPGPU_RECOMPRESS_F_BAD_CODEC.
  * LZ4 frames do not depend on the iobuf's fragmentation
  * (lz4_frame_compressor.cc:69-113), so the reference's bytes are promised

@@ -350,7 +350,8 @@ struct compressor {
     // what liblz4 / libsnappy give through those wrappers.  `frag`: the
     // size of the input iobuf's fragments (snappy-java writes one chunk per
     // fragment; 0 = one contiguous fragment).  gzip / zstd run on the host,
-    // the reference's loops over zlib / libzstd.
+    // the reference's loops over zlib / libzstd; gzip runs on the device
+    // after rpgpu_set_device_gzip(e.ctx(), 1), with the same bytes.
     static rpgpu::iobuf compress(const rpgpu::iobuf& in, type t, rpgpu::engine& e = rpgpu::engine::local(),
                                  size_t frag = 0) {
         if (t == type::none) throw std::runtime_error("compressor: nothing to compress for 'none'");
@@ -1079,6 +1080,9 @@ struct recompress_options {
     uint32_t codec = RPGPU_RECOMPRESS_SOURCE_CODEC;  // or a model::compression value for every batch
     uint64_t min_batch_bytes = 0;                    // compress_batch_consumer's threshold (0: none)
     uint64_t snappy_frag = 0;                        // the iobuf fragment size of the snappy payloads (0: one fragment)
+    bool device_gzip = false;                        // rpgpu_set_device_gzip(e.ctx(), 1) first (the context keeps it):
+                                                     // gzip batches are compressed on the device, one fragment each,
+                                                     // and a gzip topic needs no host pass
 };
 
 // The segment self_compact_segment writes, and the index it builds beside it
@@ -1107,6 +1111,7 @@ inline recompacted_segment compact_segment(const uint8_t* seg, size_t len, const
     const compacted_segment cs = detail::compact_segment_then(
       seg, len, e, [&](const detail::compact_outputs& co, compacted_segment& res) {
           rpgpu_ctx* c = e.ctx();
+          if (opt.device_gzip) e.check(rpgpu_set_device_gzip(c, 1), "rpgpu_set_device_gzip");
           const uint64_t nb = co.batches.size();
           uint64_t out_cap = 16;
           for (const auto& b : co.batches) {

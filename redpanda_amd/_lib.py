@@ -149,6 +149,9 @@ def load():
         "rpgpu_submit": (i32, [vp, C.POINTER(JobC), vp]),
         "rpgpu_last_timings": (i32, [vp, C.POINTER(C.c_float), i32]),
         "rpgpu_set_timing": (i32, [vp, i32]),
+        "rpgpu_set_device_gzip": (i32, [vp, i32]),
+        "rpgpu_gzip_device_ms": (i32, [vp, C.POINTER(C.c_float)]),
+        "rpgpu_gzip_device_payloads": (i32, [vp, C.POINTER(C.c_uint64)]),
         "rpgpu_uncompress": (i32, [vp, i32, vp, sz, vp, sz, C.POINTER(sz)]),
         "rpgpu_uncompress_batch": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "rpgpu_compress_batch": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),

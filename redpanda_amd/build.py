@@ -20,7 +20,7 @@ OUT = os.path.join(HERE, "librpgpu.so")
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("RPGPU_ARCH", "gfx950")
 
-HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip", "rp_fetch.hip", "rp_recompress.hip",
+HIP_SOURCES = ["rp_kernels.hip", "rp_validate.hip", "rp_codec.hip", "rp_inflate.hip", "rp_compress.hip", "rp_index.hip", "rp_compact.hip", "rp_append.hip", "rp_fetch.hip", "rp_recompress.hip", "rp_deflate.hip",
                "rp_runtime.hip"]
 CXX_SOURCES = ["rp_hostcodec.cpp"]
 
@@ -66,7 +66,7 @@ def build(force: bool = False, verbose: bool = False, checked: bool = False, var
     os.makedirs(bdir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(INC, "rpgpu.h"), os.path.join(CSRC, "rp_internal.h"), os.path.join(CSRC, "rp_device.h"),
-               os.path.join(CSRC, "rp_zstd_core.h")]
+               os.path.join(CSRC, "rp_zstd_core.h"), os.path.join(CSRC, "rp_deflate_core.h")]
     objs, cmds = [], []
     for src in HIP_SOURCES:
         s = os.path.join(CSRC, src)
@@ -191,6 +191,37 @@ def build_zstd_host(force: bool = False) -> str:
         os.makedirs(os.path.dirname(ZSHOST_LIB), exist_ok=True)
         _run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", ZSHOST_LIB, ZSHOST_SRC])
     return ZSHOST_LIB
+
+
+DFHOST_SRC = os.path.join(ROOT, "tests", "cpp", "deflate_core_host.cpp")
+DFHOST_LIB = os.path.join(ROOT, "tests", "cpp", "_bin", "libdfhost.so")
+
+
+def build_deflate_host(force: bool = False) -> str:
+    """rp_deflate_core.h built for the host (test infrastructure: the CPU
+    tests compare the gzip compressor the device runs with zlib itself)."""
+    hdr = os.path.join(CSRC, "rp_deflate_core.h")
+    if force or _stale(DFHOST_LIB, [DFHOST_SRC, hdr]):
+        os.makedirs(os.path.dirname(DFHOST_LIB), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", DFHOST_LIB, DFHOST_SRC])
+    return DFHOST_LIB
+
+
+GZIP_SRC = os.path.join(ROOT, "tests", "cpp", "gzip_main.cpp")
+GZIP_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "gzip_test")
+
+
+def build_gzip_test(force: bool = False) -> str:
+    """Host driver of storage::internal::compact_segment on a gzip topic with
+    recompress_options::device_gzip (include/rpgpu_redpanda.h), linked like
+    the surfaces driver."""
+    lib = build()
+    hdrs = [os.path.join(INC, "rpgpu.h"), os.path.join(INC, "rpgpu_redpanda.h")]
+    if force or _stale(GZIP_BIN, [GZIP_SRC, lib] + hdrs):
+        os.makedirs(os.path.dirname(GZIP_BIN), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", INC, GZIP_SRC, "-o", GZIP_BIN, "-L", HERE, "-l:librpgpu.so",
+              "-Wl,-rpath,$ORIGIN/../../../redpanda_amd"])
+    return GZIP_BIN
 
 
 if __name__ == "__main__":

@@ -453,6 +453,7 @@ HD uint32_t varint32_len(uint32_t v) {
 DEV uint64_t frame_bytes(uint64_t n, uint32_t first, uint32_t nbk, uint32_t codec, const CompBlock* __restrict__ blocks,
                          const uint32_t* __restrict__ sizes) {
     uint64_t o;
+    if (codec == RPGPU_CODEC_GZIP) return sizes[first];  // the gzip stream is the batch's one block
     if (codec == RPGPU_CODEC_LZ4) {
         o = n ? 15 : 7;
         for (uint32_t k = 0; k < nbk; k++) {
@@ -475,6 +476,11 @@ DEV uint64_t wave_write_frame(uint8_t* __restrict__ d, const uint8_t* __restrict
                               const uint32_t* __restrict__ sizes) {
     const uint32_t l = lane();
     uint64_t o = 0;
+    if (codec == RPGPU_CODEC_GZIP) {
+        const uint32_t c = uni32(sizes[first]);
+        wave_copy_lines(d, comp_slot(scratch, slot_off, first), c, l);
+        return c;
+    }
     if (codec == RPGPU_CODEC_LZ4) {
         uint8_t h[15];
         const uint32_t hl = lz4f_header(h, n);

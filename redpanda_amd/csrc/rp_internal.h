@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rpgpu.h"
+#include "rp_deflate_core.h"  // rp::df: the work-area size, deflateBound, takes()
 
 namespace rp {
 
@@ -506,6 +507,27 @@ hipError_t launch_compress(const uint8_t* in, const CompBlock* blocks, uint32_t 
 // scratch + slot_off[b] (slot_off null: b * kCompSlot)
 hipError_t launch_compress_blocks(const uint8_t* in, const CompBlock* blocks, uint32_t nb, uint8_t* scratch,
                                   const uint64_t* slot_off, uint32_t* sizes, bool lz4, bool snappy, hipStream_t s);
+// gzip_compressor::compress on the device (rp_deflate.hip): one stream per
+// wave (lane 0 runs rp_deflate_core.h), at most kDeflateStreams resident, each
+// over a work area of df::kWorkBytes; payloads are taken from the list
+// through a cursor.  Output slots hold df::bound(n); df::takes(n) says which
+// payloads the device accepts.  The work buffer is kDeflateCursor bytes (the
+// cursor, a fixed slot) followed by the streams' areas.
+constexpr uint32_t kDeflateStreams = 1024;
+constexpr uint64_t kDeflateCursor = 256;
+inline uint64_t deflate_work_bytes(uint32_t streams) { return kDeflateCursor + (uint64_t)streams * df::kWorkBytes; }
+struct DeflateItem {
+    uint64_t src, n;     // input bytes [src, src + n)
+    uint64_t frag, out;  // fragment size (0: one fragment); output slot offset
+};
+hipError_t launch_deflate(const uint8_t* in, const DeflateItem* items, uint32_t count, uint8_t* out, uint64_t* out_len,
+                          uint8_t* work, uint32_t streams, hipStream_t s);
+// the gzip blocks of a recompress block array (codec RPGPU_CODEC_GZIP, one
+// block per batch, one fragment): block b into scratch + slot_off[b], its
+// length into sizes[b]
+struct CompBlock;
+hipError_t launch_deflate_blocks(const uint8_t* in, const CompBlock* blocks, uint32_t nb, uint8_t* scratch,
+                                 const uint64_t* slot_off, uint32_t* sizes, uint8_t* work, uint32_t streams, hipStream_t s);
 hipError_t launch_uncompress_many(const UncItem* items, uint32_t count, const uint8_t* in, uint64_t in_total,
                                   uint8_t* out, int64_t* res, hipStream_t s);
 hipError_t launch_finalize(const DeviceJob& j, hipStream_t s);
@@ -640,6 +662,7 @@ struct RecompressArgs {
     uint64_t* spos;           // nb: rpgpu_stamp positions of the compressed batches
     uint32_t* splen;          // nb: their payload lengths
     uint32_t* counters;       // the words RecompressCounter names
+    uint32_t device_gzip;     // rpgpu_set_device_gzip: gzip batches are compressed here (one block each)
 };
 enum RecompressCounter : uint32_t {
     kRcStampCount = 0,   // compressed batches to stamp: k_recompress_pack lists them; k_stamp (its d_n)

@@ -19,6 +19,10 @@
 //                block array is zeroed and the block kernels run over its bound)
 //   k_compress_blocks    (rp_compress.hip) one wave per block, from the payload
 //                where it lies in the input log
+//   k_deflate_blocks     (rp_deflate.hip) with rpgpu_set_device_gzip: a gzip
+//                batch is ONE block of the same array (codec gzip, its scratch
+//                slot the deflateBound), compressed as one fragment by one
+//                lane; its frame is that block's bytes
 //   k_recompress_layout_sizes  one thread per batch: its output bytes (the
 //                frame's length from the block sizes), its pack pieces
 //   (scans)      output position, output ordinal / first piece
@@ -58,6 +62,8 @@ DEV bool not_written(const RecompressArgs& a) {
 HD uint64_t slot_bytes(uint32_t codec, uint64_t n) {
     return ((codec == RPGPU_CODEC_SNAPPY ? 32 + n + n / 6 : n) + 15) & ~15ull;
 }
+// a gzip batch's slot: deflateBound on the 16-byte slot grid
+HD uint64_t gzip_slot(uint64_t n) { return (df::bound(n) + 15) & ~15ull; }
 struct Geom {
     uint64_t blocks, scratch;
 };
@@ -133,6 +139,17 @@ __global__ __launch_bounds__(256) void k_recompress_sizes(RecompressArgs a) {
                     mode |= kRcCompress;
                     g = batch_geom(codec, plen, fr);
                 }
+            } else if (codec == RPGPU_CODEC_GZIP && a.device_gzip) {
+                // rpgpu_set_device_gzip: one block (one stream of k_deflate_blocks, one fragment), its
+                // scratch slot the deflateBound
+                if (!df::takes(plen)) {
+                    flags = RPGPU_RECOMPRESS_F_TOO_LARGE;
+                } else {
+                    flags = RPGPU_RECOMPRESS_F_COMPRESSED;
+                    mode |= kRcCompress;
+                    g.blocks = 1;
+                    g.scratch = gzip_slot(plen);
+                }
             } else if (codec == RPGPU_CODEC_GZIP || codec == RPGPU_CODEC_ZSTD) {
                 flags = RPGPU_RECOMPRESS_F_HOST;
             } else if (codec != RPGPU_CODEC_NONE) {
@@ -160,8 +177,19 @@ __global__ __launch_bounds__(256) void k_recompress_fill(RecompressArgs a) {
     const uint32_t codec = mode & 0xFF;
     const rpgpu_compact_batch& e = a.job.d_in_batches[b];
     const uint64_t plen = e.payload_len, src = e.out_pos + RPGPU_HEADER_SIZE;
-    const uint64_t fr = frag_size(codec, plen, a.job.snappy_frag);
     uint64_t k = a.bblk[b], so = a.bscr[b];
+    if (codec == RPGPU_CODEC_GZIP) {
+        CompBlock c;
+        c.src = src;
+        c.n = (uint32_t)plen;
+        c.codec = codec;
+        c.frag_len = (uint32_t)plen;
+        c.frag_blocks = 1;
+        a.blocks[k] = c;
+        a.slot_off[k] = so;
+        return;
+    }
+    const uint64_t fr = frag_size(codec, plen, a.job.snappy_frag);
     for (uint64_t f = 0; f < plen; f += fr) {
         const uint64_t flen = plen - f < fr ? plen - f : fr;
         const uint32_t nbk = (uint32_t)((flen + 65535) >> 16);

@@ -203,6 +203,15 @@ struct rpgpu_ctx {
     uint32_t hc_n = 0;
     Buf gz_pool;   // gzip / zstd first-pass output pool (k_members_first)
     Buf gzs_pool;  // the gzip split decode's chunk symbols
+    // rpgpu_set_device_gzip: gzip payloads are deflated on the device
+    // (k_deflate, k_deflate_blocks); dfw: the list cursor, then the streams'
+    // work areas (grow-only, at most kDeflateStreams of df::kWorkBytes); dev:
+    // k_deflate's events in rpgpu_compress_batch (rpgpu_set_timing)
+    bool device_gzip = false;
+    uint64_t gzip_dev_payloads = 0;
+    Buf dfw;
+    hipEvent_t dev[2] = {nullptr, nullptr};
+    bool dev_live = false;
 };
 
 namespace {
@@ -466,7 +475,7 @@ int rpgpu_destroy(rpgpu_ctx* c) {
         if (sd->join_ev) (void)hipEventDestroy(sd->join_ev);
     }
     if (c->copy) { (void)hipStreamSynchronize(c->copy); (void)hipStreamDestroy(c->copy); }
-    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->fws, &c->rws, &c->seqs, &c->pool, &c->fpool,
+    for (Buf* b : {&c->ws, &c->uws, &c->qws, &c->bh, &c->bd, &c->sws, &c->iws, &c->cws, &c->aws, &c->fws, &c->rws, &c->dfw, &c->seqs, &c->pool, &c->fpool,
                    &c->sth, &c->std_, &c->hc_items, &c->hc_items_h, &c->hc_in, &c->hc_in_h, &c->hc_out, &c->hc_out_h,
                    &c->hc_small, &c->gz_pool, &c->gzs_pool})
         b->release();
@@ -485,6 +494,8 @@ int rpgpu_destroy(rpgpu_ctx* c) {
     for (hipEvent_t e : c->fev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->rev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->dev)
         if (e) hipEventDestroy(e);
     if (c->ws_ev) (void)hipEventDestroy(c->ws_ev);
     for (auto& set : c->ev_sets)
@@ -557,6 +568,26 @@ int rpgpu_sync(rpgpu_ctx* c, void* s) {
 int rpgpu_set_timing(rpgpu_ctx* c, int enable) {
     if (!c) return RPGPU_E_INVALID;
     c->timing = enable != 0;
+    return RPGPU_OK;
+}
+
+int rpgpu_set_device_gzip(rpgpu_ctx* c, int enable) {
+    if (!c) return RPGPU_E_INVALID;
+    c->device_gzip = enable != 0;
+    return RPGPU_OK;
+}
+
+int rpgpu_gzip_device_ms(rpgpu_ctx* c, float* ms) {
+    if (!c || !ms) return RPGPU_E_INVALID;
+    if (!c->dev_live) return fail(c, RPGPU_E_INVALID, "rpgpu_gzip_device_ms: no timed device gzip in rpgpu_compress_batch");
+    HIPCHK(c, hipEventSynchronize(c->dev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->dev[0], c->dev[1]));
+    return RPGPU_OK;
+}
+
+int rpgpu_gzip_device_payloads(rpgpu_ctx* c, uint64_t* n) {
+    if (!c || !n) return RPGPU_E_INVALID;
+    *n = c->gzip_dev_payloads;
     return RPGPU_OK;
 }
 
@@ -1538,6 +1569,12 @@ int rpgpu_recompress(rpgpu_ctx* c, const rpgpu_recompress_job* job, void* stream
     const size_t o_scan = take(scan_temp_bytes(nb) + 64), o_cnt = take(256), o_scr = take(scratch_cap + 16);
     need += 256;
     if (int rc = grow(c, c->rws, need, s, "rpgpu_recompress workspace")) return rc;
+    // gzip batches (rpgpu_set_device_gzip): one stream each, at most one per input batch
+    const bool dgzip = c->device_gzip && nb &&
+                       (job->codec == RPGPU_RECOMPRESS_SOURCE_CODEC || job->codec == RPGPU_CODEC_GZIP);
+    const uint32_t dstreams = (uint32_t)std::min<uint64_t>(nb, kDeflateStreams);
+    if (dgzip)
+        if (int rc = grow(c, c->dfw, deflate_work_bytes(dstreams), s, "gzip work areas")) return rc;
     ScratchScope scratch(c, s);
     if (int rc = scratch.acquired()) return rc;
     uint8_t* w = c->rws.as<uint8_t>();
@@ -1568,6 +1605,7 @@ int rpgpu_recompress(rpgpu_ctx* c, const rpgpu_recompress_job* job, void* stream
         }
         return hipEventRecord(c->rev[i], s);
     };
+    a.device_gzip = c->device_gzip ? 1u : 0u;
     c->rev_live = false;
     HIPCHK(c, mark(0));
     // the scans leave the totals at [nb]; without batches these zeroes are the totals
@@ -1582,6 +1620,9 @@ int rpgpu_recompress(rpgpu_ctx* c, const rpgpu_recompress_job* job, void* stream
         const bool any = job->codec == RPGPU_RECOMPRESS_SOURCE_CODEC;
         HIPCHK(c, launch_compress_blocks(job->d_in, a.blocks, (uint32_t)block_cap, a.scratch, a.slot_off, a.sizes,
                                          any || job->codec == RPGPU_CODEC_LZ4, any || job->codec == RPGPU_CODEC_SNAPPY, s));
+        if (dgzip)
+            HIPCHK(c, launch_deflate_blocks(job->d_in, a.blocks, (uint32_t)block_cap, a.scratch, a.slot_off, a.sizes,
+                                            c->dfw.as<uint8_t>(), dstreams, s));
     }
     HIPCHK(c, mark(2));
     HIPCHK(c, launch_recompress_layout(a, w + o_scan, scan_temp_bytes(nb) + 64, s));
@@ -1940,12 +1981,30 @@ int rpgpu_compress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const void
     // the block kernels' dword reads assume
     struct Stage { const uint8_t* src; uint64_t n, off; };
     std::vector<Stage> stage;
+    // gzip payloads the device takes (rpgpu_set_device_gzip): one k_deflate
+    // stream each, its output slot among the frames'
+    std::vector<uint32_t> dfl_dev;
+    std::vector<DeflateItem> dfl;
     uint64_t in_total = 0, out_total = 0;
     for (uint32_t i = 0; i < n; i++) {
         out_len[i] = 0;
         const int codec = codecs[i];
         if (codec < 0 || codec > RPGPU_CODEC_ZSTD || (!in[i] && in_len[i])) { status[i] = RPGPU_E_INVALID; continue; }
         if (codec == RPGPU_CODEC_NONE) { status[i] = RPGPU_E_CODEC; continue; }
+        if (codec == RPGPU_CODEC_GZIP && c && c->device_gzip && df::takes(in_len[i])) {
+            DeflateItem it;
+            it.src = in_total;
+            it.n = in_len[i];
+            it.frag = frag ? frag[i] : 0;
+            it.out = out_total;
+            stage.push_back({(const uint8_t*)in[i], it.n, in_total});
+            in_total += align_up(it.n + 8, 16);
+            out_total += align_up(df::bound(it.n), 16);
+            dfl.push_back(it);
+            dfl_dev.push_back(i);
+            status[i] = RPGPU_E_CODEC;
+            continue;
+        }
         if (codec == RPGPU_CODEC_GZIP || codec == RPGPU_CODEC_ZSTD) {
             // the CPU fallback: the reference's loops over zlib / libzstd
             const int r = host_compress(codec, (const uint8_t*)in[i], in_len[i], frag ? frag[i] : 0, (uint8_t*)out[i],
@@ -1999,15 +2058,17 @@ int rpgpu_compress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const void
         out_total += align_up(rpgpu_compress_bound(codec, len, fr), 16);
         status[i] = RPGPU_E_CODEC;
     }
-    if (pays.empty()) return RPGPU_OK;
+    if (pays.empty() && dfl.empty()) return RPGPU_OK;
     hipSetDevice(c->device);
     hipStream_t s = c->stream;
-    const uint32_t np = (uint32_t)pays.size(), nb = (uint32_t)blocks.size();
-    // device: [inputs][blocks][payloads] | [out_len][sizes][outputs][scratch];
-    // host (pinned): the first part, then out_len + outputs coming back
+    const uint32_t np = (uint32_t)pays.size(), nb = (uint32_t)blocks.size(), nd = (uint32_t)dfl.size();
+    // device: [inputs][blocks][payloads][deflate items] | [out_len: frames,
+    // then gzip streams][sizes][outputs][scratch]; host (pinned): the first
+    // part, then out_len + outputs coming back
     const size_t o_blk = align_up(in_total + 16, 256), o_pay = align_up(o_blk + (size_t)nb * sizeof(CompBlock), 256);
-    const size_t o_len = align_up(o_pay + (size_t)np * sizeof(CompPayload), 256);
-    const size_t o_sz = align_up(o_len + (size_t)np * 8, 256), o_out = align_up(o_sz + (size_t)nb * 4, 256);
+    const size_t o_dfi = align_up(o_pay + (size_t)np * sizeof(CompPayload), 256);
+    const size_t o_len = align_up(o_dfi + (size_t)nd * sizeof(DeflateItem), 256);
+    const size_t o_sz = align_up(o_len + (size_t)(np + nd) * 8, 256), o_out = align_up(o_sz + (size_t)nb * 4, 256);
     const size_t o_scr = align_up(o_out + out_total, 256), total = o_scr + (size_t)nb * kCompSlot;
     if (int rc = grow(c, c->bd, total, s, "compress staging")) return rc;
     if (int rc = grow(c, c->bh, o_scr, s, "compress pinned staging")) return rc;
@@ -2018,10 +2079,27 @@ int rpgpu_compress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const void
         if (st.n) std::memcpy(h + st.off, st.src, st.n);
     std::memcpy(h + o_blk, blocks.data(), nb * sizeof(CompBlock));
     std::memcpy(h + o_pay, pays.data(), np * sizeof(CompPayload));
+    if (nd) std::memcpy(h + o_dfi, dfl.data(), nd * sizeof(DeflateItem));
+    const uint32_t streams = std::min(nd, kDeflateStreams);
+    if (nd)
+        if (int rc = grow(c, c->dfw, deflate_work_bytes(streams), s, "gzip work areas")) return rc;
+    const bool dtimed = nd && c->timing;
+    c->dev_live = false;
+    if (dtimed)
+        for (int k = 0; k < 2; k++)
+            if (!c->dev[k]) HIPCHK(c, hipEventCreate(&c->dev[k]));
     HIPCHK(c, hipMemcpyAsync(d, h, o_len, hipMemcpyHostToDevice, s));
     HIPCHK(c, launch_compress(d, (const CompBlock*)(d + o_blk), nb, (const CompPayload*)(d + o_pay), np, d + o_scr,
                               (uint32_t*)(d + o_sz), d + o_out, (uint64_t*)(d + o_len), s));
-    HIPCHK(c, hipMemcpyAsync(h + o_len, d + o_len, np * 8, hipMemcpyDeviceToHost, s));
+    if (dtimed) HIPCHK(c, hipEventRecord(c->dev[0], s));
+    if (nd)
+        HIPCHK(c, launch_deflate(d, (const DeflateItem*)(d + o_dfi), nd, d + o_out, (uint64_t*)(d + o_len) + np,
+                                 c->dfw.as<uint8_t>(), streams, s));
+    if (dtimed) {
+        HIPCHK(c, hipEventRecord(c->dev[1], s));
+        c->dev_live = true;
+    }
+    HIPCHK(c, hipMemcpyAsync(h + o_len, d + o_len, (size_t)(np + nd) * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(h + o_out, d + o_out, out_total, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const uint64_t* lens = (const uint64_t*)(h + o_len);
@@ -2032,6 +2110,14 @@ int rpgpu_compress_batch(rpgpu_ctx* c, uint32_t n, const int* codecs, const void
         std::memcpy(out[i], h + o_out + pays[k].out, out_len[i]);
         status[i] = RPGPU_OK;
     }
+    for (uint32_t k = 0; k < nd; k++) {
+        const uint32_t i = dfl_dev[k];
+        out_len[i] = (size_t)lens[np + k];
+        if (out_len[i] > cap[i]) { status[i] = RPGPU_E_OVERFLOW; continue; }
+        std::memcpy(out[i], h + o_out + dfl[k].out, out_len[i]);
+        status[i] = RPGPU_OK;
+    }
+    c->gzip_dev_payloads += nd;
     return RPGPU_OK;
 }
 

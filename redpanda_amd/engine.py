@@ -375,10 +375,30 @@ class Engine:
         check(self.L.rpgpu_uncompress_batch(self.ctx, n, ci, ip, il, op, oc, ol, st), self.ctx, "rpgpu_uncompress_batch")
         return [(int(st[i]), outs[i][: ol[i]].tobytes() if st[i] == 0 else int(ol[i])) for i in range(n)]
 
+    def set_device_gzip(self, on: bool = True):
+        """rpgpu_set_device_gzip: gzip payloads of compress_batch and gzip
+        batches of recompress are deflated on the device (zlib 1.2.11's
+        bytes); off by default."""
+        check(self.L.rpgpu_set_device_gzip(self.ctx, 1 if on else 0), self.ctx, "rpgpu_set_device_gzip")
+
+    def gzip_device_ms(self) -> float:
+        """Device milliseconds of k_deflate in the last compress_batch run
+        under set_timing() with set_device_gzip()."""
+        ms = C.c_float(0)
+        check(self.L.rpgpu_gzip_device_ms(self.ctx, C.byref(ms)), self.ctx, "rpgpu_gzip_device_ms")
+        return float(ms.value)
+
+    def gzip_device_payloads(self) -> int:
+        """gzip payloads this context has compressed on the device so far"""
+        n = C.c_uint64(0)
+        check(self.L.rpgpu_gzip_device_payloads(self.ctx, C.byref(n)), self.ctx, "rpgpu_gzip_device_payloads")
+        return int(n.value)
+
     def compress_batch(self, codecs, payloads, frags=None, caps=None):
         """rpgpu_compress_batch (compressor::compress on the device): [(status,
         bytes)] per payload — lz4 frames / snappy-java streams (frags[i]: the
-        iobuf fragment size, 0 = one fragment)."""
+        iobuf fragment size, 0 = one fragment); gzip / zstd on the host, gzip
+        on the device after set_device_gzip()."""
         n = len(payloads)
         srcs = [np.frombuffer(bytes(p), dtype=np.uint8) if len(p) else np.zeros(1, np.uint8) for p in payloads]
         frags = list(frags) if frags is not None else [0] * n
@@ -603,7 +623,9 @@ class Engine:
         compressed again on the device (do_compaction's compress_batch): LZ4
         and snappy batches become what compress_batch gives (snappy over
         snappy_frag-byte fragments), headers restamped; gzip / zstd ones stay
-        uncompressed, flagged abi.RECOMPRESS_F_HOST for the host to finish.
+        uncompressed, flagged abi.RECOMPRESS_F_HOST for the host to finish
+        (after set_device_gzip() gzip ones are compressed here too, one
+        fragment each, and only zstd is left to the host).
         codec: abi.RECOMPRESS_SOURCE_CODEC (each batch its source codec) or
         one codec for every batch; min_batch_bytes: smaller batches pass
         through.  Returns device tensors (the segments, and the batch results
